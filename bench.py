@@ -1,6 +1,14 @@
 """Benchmark: factor·asset·days/s of the device-resident ops + IC + selection pipeline.
 
     python bench.py --gpus N --steps K --warmup W [--workload c2|c4|c5] [--dates D ...]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line; ``--full``
+adds the host measurement behind ``cpu_baseline`` (null in a plain run's line).
+``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy (panels at
+fixed seeded positions; every file finite: the values in float64 with 0 where a result is
+NaN or infinite, and <name>_nonfinite.npy marking those places): the same arguments give
+the same inputs, so two builds compare output for output.
 
 Default workload = BASELINE.json configs[1] (C2): 2,520 dates x 5,000 assets x 200
 factors, synthetic data (SURVEY 8(d) generator, generated on the device).  A "step" is
@@ -18,8 +26,8 @@ Other workloads (BASELINE configs[3], [4]; parity cases, not the driver's line):
       icir_top weights and the weighted composite (zscore) of the feature panel.
 
 Rank 0 prints one JSON line (driver contract) with ``roofline`` (dominant kernel,
-HIP-event timed inside the timed steps), ``cpu_baseline`` (the numpy oracle port on a
-bounded sample, 16 host processes) and ``reference_cpu`` (the reference itself, timed in
+HIP-event timed inside the timed steps), ``cpu_baseline`` (with ``--full``: the numpy oracle
+port on a bounded sample, 16 host processes) and ``reference_cpu`` (the reference itself, timed in
 the build container: SURVEY.md §6).
 """
 from __future__ import annotations
@@ -132,12 +140,21 @@ def parse():
     p.add_argument("--dates", type=int, default=None)
     p.add_argument("--assets", type=int, default=None)
     p.add_argument("--factors", type=int, default=None)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also time the numpy oracle port on the host (cpu_baseline); a plain run leaves it out")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step computed as DIR/<name>.npy (c2/c4/c5)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline all the same")
     p.add_argument("--cpu-workers", type=int, default=16, help="host processes of the CPU port baseline")
     p.add_argument("--stages", action="store_true", help="print per-stage times to stderr")
     p.add_argument("--selftest-dist", action="store_true",
                    help="CPU/gloo check of the rank launcher only (tests/test_bench_launch.py)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload not in WORKLOAD_DIMS:
+        p.error("--dump-outputs covers the c2 / c4 / c5 workloads")
+    return args
 
 
 def _port_worker(args):
@@ -490,6 +507,48 @@ def dropin_bench(args):
     print(json.dumps(line))
 
 
+DUMP_SAMPLE = 400_000          # elements per dumped array (3.2 MB of f64 + 1.6 MB of f32 marks)
+
+
+def _dump_array(stem, t, rng, own_lo=0):
+    """``t`` as two finite .npy files: whole when it has at most DUMP_SAMPLE elements, else
+    its values at DUMP_SAMPLE positions drawn from ``rng`` (dimension 1 from ``own_lo`` on: a
+    shard's halo rows are not its results).  <stem>.npy (float64) holds the values with 0
+    where the result is not finite -- the panels carry NaN by design (missing data, window
+    warm-up) -- and <stem>_nonfinite.npy (float32) says which: 0 finite, 1 NaN, 2 +inf, 3 -inf."""
+    if t.numel() > DUMP_SAMPLE:
+        lo = [own_lo if k == 1 else 0 for k in range(t.dim())]
+        idx = tuple(torch.as_tensor(rng.integers(lo[k], n, DUMP_SAMPLE), device=t.device)
+                    for k, n in enumerate(t.shape))
+        t = t[idx]
+    v = t.detach().to(torch.float64).cpu().numpy()
+    mark = np.zeros(v.shape, dtype=np.float32)
+    mark[np.isnan(v)] = 1.0
+    mark[v == np.inf] = 2.0
+    mark[v == -np.inf] = 3.0
+    np.save(stem + ".npy", np.where(mark == 0, v, 0.0))
+    np.save(stem + "_nonfinite.npy", mark)
+
+
+def dump_outputs(outdir, sp, cfg, w, kept):
+    """What the last timed step handed its caller, as finite .npy files under ``outdir``
+    (_dump_array): the selection weights [J][F] and the kept factor list run_step returned,
+    and the panels the step wrote -- its operator output buffers (as the last stage to use
+    each left it) and the C5 feature panel -- at fixed positions (seed 0: the same from run
+    to run)."""
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng(0)
+    if w is not None:
+        _dump_array(os.path.join(outdir, "weights"), w, rng)
+    if kept is not None:
+        np.save(os.path.join(outdir, "kept.npy"), np.asarray(kept, dtype=np.float64))
+    if cfg.ops:
+        for i, b in enumerate(getattr(sp, "bufs", None) or []):
+            _dump_array(os.path.join(outdir, f"op_buffer_{i}"), b, rng, sp.halo)
+    if any(op == "corr_vol" for op, _ in cfg.ret_ops):
+        _dump_array(os.path.join(outdir, "feature"), sp.feature, rng, sp.halo)
+
+
 def main():
     args = parse()
     if args.workload in ("c1-dropin", "c2-dropin-slice"):
@@ -515,7 +574,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # before this process initialises the GPU: the port's workers are spawned children
         dims0 = WORKLOAD_DIMS[args.workload]
         Db, Ab, Fb = args.dates or dims0[0], args.assets or dims0[1], args.factors or dims0[2]
@@ -565,7 +624,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        PL.run_step(sp, cfg, timers=timers)
+        w_last, kept_last = PL.run_step(sp, cfg, timers=timers)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -575,6 +634,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     stages = PL.stage_times(timers)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sp, cfg, w_last, kept_last)
     ms_step = dt / args.steps * 1e3
     units = float(D) * A * F
     value = units / (dt / args.steps)

@@ -13,7 +13,7 @@ for s in "$@"; do
     tests) specs+=("tests_$TAG:500:python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread") ;;
     t:*) specs+=("t_$TAG:400:python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread -k '${s#t:}'") ;;
     smoke) specs+=("smoke_$TAG:200:python -c 'import __graft_entry__ as g; g.smoke()'") ;;
-    bench) specs+=("bench_$TAG:300:python bench.py --steps 20 --warmup 5") ;;
+    bench) specs+=("bench_$TAG:300:python bench.py --full --steps 20 --warmup 5") ;;
     bench:*) specs+=("bench_$TAG:400:python bench.py ${s#bench:}") ;;
     stages) specs+=("stages_$TAG:300:python bench.py --steps 5 --warmup 2 --stages --no-cpu-baseline") ;;
     prof) specs+=("prof_$TAG:300:rocprofv3 --kernel-trace --stats -f csv -d gpurun_out/prof_$TAG -o run -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline") ;;
