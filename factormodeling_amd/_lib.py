@@ -59,6 +59,10 @@ SIGNATURES = {
                               c_i64, c_vp, c_vp],
     "fmx_ic_window": [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp],
     "fmx_select_icir_top": [c_vp, c_i64, c_i64, c_i32, c_dbl, c_i32, c_vp, c_vp, c_vp],
+    "fmx_mvo_covariance": [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp],
+    "fmx_mvo_windows": [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_vp, c_i32, c_i32, c_dbl, c_vp,
+                        c_vp, c_vp, c_i64, c_vp],
+    "fmx_mvo_windows_work_bytes": [c_i64, c_i64, c_i64],
     "fmx_zscore_exposures": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp],
     "fmx_corr_prune_windows": [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32,
                                c_dbl, c_dbl, c_i32, c_vp, c_vp, c_i64, c_vp],
@@ -103,6 +107,7 @@ _RESTYPES = {"fmx_last_error": c_cp, "fmx_build_variant": c_cp, "fmx_ic_ranked_w
              "fmx_group_op_long_work_bytes": c_i64,
              "fmx_gram_fused_work_bytes": c_i64, "fmx_corr_prune_windows_work_bytes": c_i64,
              "fmx_cs_rank_sorted_work_bytes": c_i64, "fmx_group_rank_sorted_work_bytes": c_i64, "fmx_gram_exact_work_bytes": c_i64,
+             "fmx_mvo_windows_work_bytes": c_i64,
              "fmx_debug_exact_fold": None}
 
 # constants mirrored from include/fmx.h

@@ -1,6 +1,8 @@
 """Loader for the reference's own HOST-ONLY modules (outside the GPU scope):
 the MVO trade-list solvers (portfolio_simulation.py:183-248, :315-746) and
-``mvo_selector`` (factor_selection_methods.py:119-175), both cvxpy / scipy QPs per date.
+``mvo_selector`` (factor_selection_methods.py:119-175) when it is called directly or with
+``backend="reference"``, both cvxpy / scipy QPs per date.  ``FactorSelector(method="mvo")``
+itself runs on the device (``engine.mvo_windows``) and never comes here.
 
 They are loaded by file path from ``$FMX_REFERENCE_DIR`` under a private module name.
 The directory is on ``sys.path`` only while the module body executes (its top-level

@@ -478,6 +478,56 @@ def select_icir_top(metrics, use_rank_icir=True, threshold=0.03, top_x=5):
     return order, w
 
 
+MVO_MAX_F = 256
+
+
+def _mvo_inputs(fret, d0, d1):
+    if not isinstance(fret, torch.Tensor) or fret.device.type != "cuda" or fret.dtype != F64 or fret.dim() != 2:
+        raise _lib.FmxError("mvo: fret must be a float64 [D][F] HIP device tensor")
+    D, F = fret.shape
+    if not 2 <= F <= MVO_MAX_F:
+        raise _lib.FmxError(f"mvo: 2 <= F <= {MVO_MAX_F} factors supported, got {F}")
+    d0t = torch.as_tensor(np.asarray(d0, dtype=np.int32), device=fret.device)
+    d1t = torch.as_tensor(np.asarray(d1, dtype=np.int32), device=fret.device)
+    if d0t.dim() != 1 or d0t.shape != d1t.shape:
+        raise _lib.FmxError("mvo: d0 and d1 must be 1-D and of equal length")
+    return fret.contiguous(), int(D), int(F), d0t, d1t, len(d0t)
+
+
+def mvo_covariance(fret, d0, d1, use_shrinkage=True):
+    """Per-window moments of the factor returns fret [D][F] over the rows [d0[j], d1[j])
+    (fmx_mvo_covariance): mu [J][F], cov [J][F][F] (Ledoit-Wolf constant-correlation shrunk,
+    or the ddof=1 sample covariance), lam [J].  Rejected windows (n < 2, NaN / inf) are NaN."""
+    fret, D, F, d0t, d1t, J = _mvo_inputs(fret, d0, d1)
+    mu = torch.empty((J, F), dtype=F64, device=fret.device)
+    cov = torch.empty((J, F, F), dtype=F64, device=fret.device)
+    lam = torch.empty((J,), dtype=F64, device=fret.device)
+    call("fmx_mvo_covariance", ptr(fret), D, F, ptr(d0t), ptr(d1t), J, int(bool(use_shrinkage)), ptr(mu), ptr(cov),
+         ptr(lam), stream_ptr())
+    return mu, cov, lam
+
+
+def mvo_windows(fret, d0, d1, risk_aversion=1.0, max_weight=1.0, turnover_penalty=0.0, prev=None, use_shrinkage=True,
+                max_iter=20000, eps=1e-9):
+    """mvo_selector's QP for every window at once (fmx_mvo_windows): w [J][F] and info [J][6]
+    = status (0 converged, 1 max_iter reached, 2 no solution: window rejected or
+    F * max_weight < 1; zero row), iterations, primal residual, dual residual, lambda, rho.
+    prev: [F] previous weights (device or host) or None."""
+    fret, D, F, d0t, d1t, J = _mvo_inputs(fret, d0, d1)
+    if prev is not None:
+        prev = torch.as_tensor(prev, dtype=F64).to(fret.device).contiguous()
+        if tuple(prev.shape) != (F,):
+            raise _lib.FmxError("mvo_windows: prev must hold one weight per factor")
+    w = torch.empty((J, F), dtype=F64, device=fret.device)
+    info = torch.empty((J, 6), dtype=F64, device=fret.device)
+    nb = int(_lib.load().fmx_mvo_windows_work_bytes(D, F, J))
+    work, wb = _workspace_bytes(fret.device, nb)
+    call("fmx_mvo_windows", ptr(fret), D, F, ptr(d0t), ptr(d1t), J, float(risk_aversion), float(max_weight),
+         float(turnover_penalty), ptr(prev), int(bool(use_shrinkage)), int(max_iter), float(eps), ptr(w), ptr(info),
+         ptr(work), wb, stream_ptr())
+    return w, info
+
+
 def zscore_exposures(X, stats=None):
     """Z (per-date z-score, NaN -> 0, sigma in {0, NaN} -> row 0) and M (bf16 0/1) from
     the numpy-pairwise row moments of cs_moment_stats (the oracle's, bit for bit)."""

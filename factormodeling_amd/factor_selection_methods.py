@@ -4,10 +4,11 @@ The selector functions keep the reference's plugin signature
 ``f(metrics_df, factors_win, returns_win, factor_ret_win, today, window, **kwargs) ->
 pd.Series`` (factor_selection_methods.py:6, :28, :119) so user code and the
 ``FACTOR_SELECTION_METHODS`` registry keep working.  icir_top and momentum are O(F) numpy
-functions; mvo (a cvxpy QP) is the reference's own selector, loaded by path.  The
-O(D x A x F) work they consume (window metrics) is computed on the GPU by
-``factor_selector``, which also runs ``icir_top`` fully on the device when the registry
-entry is the built-in one.
+functions; ``mvo_selector`` called directly is the reference's own cvxpy selector, loaded by
+path.  The O(D x A x F) work they consume (window metrics) is computed on the GPU by
+``factor_selector``, which also runs ``icir_top`` and ``mvo`` fully on the device when the
+registry entry is the built-in one (mvo: ``engine.mvo_windows``, every day's covariance and
+QP in one call, unless ``backend="reference"`` is passed).
 
 ``corr_prune_selector`` is builder-defined (no reference counterpart): it
 prunes the ICIR ranking greedily by the fp64-MFMA factor-correlation matrix.
@@ -78,11 +79,12 @@ def ledoit_wolf_shrinkage(returns):
 
 def mvo_selector(metrics_df, factors_win, returns_win, factor_ret_win, today, window, risk_aversion=1.0,
                  max_weight=1.0, turnover_penalty=0.0, previous_weights=None, use_shrinkage=True, **kwargs):
-    """Mean-variance factor weights (factor_selection_methods.py:119-175): a host cvxpy QP,
-    outside the GPU scope.  Handed to the reference's own selector, loaded by path from
+    """Mean-variance factor weights (factor_selection_methods.py:119-175) for one day, as
+    a host cvxpy QP: handed to the reference's own selector, loaded by path from
     ``$FMX_REFERENCE_DIR`` (``_refload``, as the drop-in ``Simulation`` does for its MVO
     methods), so the solver setup is the reference's exactly; it needs cvxpy like the
-    reference."""
+    reference.  ``FactorSelector(method="mvo")`` does not come here: it solves every day on
+    the device (``engine.mvo_windows``) unless ``backend="reference"`` is passed."""
     from . import _refload
     mod = _refload.load("factor_selection_methods.py", "mvo_selector")
     return mod.mvo_selector(metrics_df, factors_win, returns_win, factor_ret_win, today, window,

@@ -5,7 +5,10 @@ attributes, logging and outputs (factor_selector.py:26-139).  The per-(factor, d
 Pearson/rank IC and beta loop (two ``pearsonr`` + one ``rankdata`` Python calls per
 group in the reference) runs as one ``fmx_ic_daily`` launch over the whole panel, and
 the rolling-window metrics of every processed day come from one ``fmx_ic_window``
-launch over the daily series.
+launch over the daily series.  The built-in ``icir_top``, ``corr_prune`` and ``mvo`` rules
+then run for every processed day at once on the device (``mvo``: ``fmx_mvo_windows``, the
+Ledoit-Wolf covariance and the QP of each day's window); other registry entries keep the
+reference's host loop.
 
 Rolling selection, dense panels: ``FactorSelector`` shifts factors by one row per symbol
 and ``single_factor_metrics`` shifts again inside each window (factor_selector.py:84,
@@ -156,22 +159,11 @@ class FactorSelector:
             out.append(engine.ic_window(dl, [0], [len(wd)])[0])
         return torch.stack(out) if out else torch.empty((0, X.shape[0], 8), dtype=torch.float64, device=dev)
 
-    def prepare_selection(self) -> pd.DataFrame:
-        """factor_selector.py:94-139"""
-        if self.factor_selection is not None:
-            logger.info("Factor selection already prepared. Returning cached result.")
-            return self.factor_selection
-        logger.info("Executing rolling factor selection...")
-        proc_dates = self.dates[self.window:-1]
-        selector_func = FACTOR_SELECTION_METHODS.get(self.method)
-        if selector_func is None:
-            raise ValueError(f"Unknown factor selection method: {self.method}")
-        if not proc_dates:
-            self.factor_selection = pd.DataFrame()
-            return self.factor_selection
+    def _select_general(self, selector_func, proc_dates, proc_idx) -> pd.DataFrame:
+        """Every selector but the native MVO: the device rules for the built-in icir_top / corr_prune,
+        else the reference's host loop over the processed days."""
         names = self.factor_cols
         P, X, R = _dense_inputs(self._factors_raw[names], self.returns)
-        proc_idx = list(range(self.window, len(self.dates) - 1))
         M = self._window_metrics(P, X, R, proc_idx)                     # [J][F][8] on device
         kw = self.method_kwargs
         device_prune = (selector_func is corr_prune_selector and P.dense and len(names) <= engine.FUSED_GRAM_MAX_F
@@ -213,6 +205,71 @@ class FactorSelector:
                 vec.name = today
                 vecs.append(vec)
             sel = pd.concat(vecs, axis=1).T
+        return sel
+
+    def _mvo_native(self, selector_func) -> bool:
+        """The built-in mvo_selector runs on the device (``engine.mvo_windows``) unless
+        ``backend="reference"`` asks for the reference's own cvxpy selector, F is outside
+        2..256 or factor_ret_df's index cannot be gathered as one [dates][F] block."""
+        if selector_func is not mvo_selector or self.method_kwargs.get("backend") == "reference":
+            return False
+        if not 2 <= len(self.factor_cols) <= engine.MVO_MAX_F:
+            return False
+        idx = pd.Index(self.factor_ret_df.index)
+        return bool(idx.is_unique and (idx.get_indexer(pd.Index(self.dates)) >= 0).all())
+
+    def _select_mvo_device(self, proc_dates, proc_idx) -> pd.DataFrame:
+        """mvo_selector for every processed day in one launch: the windows [i - W, i) of the
+        factor returns gathered once.  The rule reads metrics_df only for its index, so the
+        window metrics are computed for the first processed day alone (its rank_IC_IR order
+        is the result's column order, as in the icir_top branch)."""
+        names = self.factor_cols
+        kw = self.method_kwargs
+        P, X, R = _dense_inputs(self._factors_raw[names], self.returns)
+        M0 = self._window_metrics(P, X, R, proc_idx[:1])
+        with phase("pandas->dense"):
+            fr = self.factor_ret_df.loc[self.dates, names].to_numpy(dtype=np.float64, na_value=np.nan)
+            prev = kw.get("previous_weights")
+            if prev is not None:
+                prev = prev.reindex(names).fillna(0).to_numpy(dtype=np.float64)
+        fret = torch.as_tensor(np.ascontiguousarray(fr), device=X.device)
+        w, info = engine.mvo_windows(fret, [i - self.window for i in proc_idx], proc_idx,
+                                     risk_aversion=kw.get("risk_aversion", 1.0), max_weight=kw.get("max_weight", 1.0),
+                                     turnover_penalty=kw.get("turnover_penalty", 0.0), prev=prev,
+                                     use_shrinkage=kw.get("use_shrinkage", True), max_iter=kw.get("max_iter", 20000),
+                                     eps=kw.get("eps", 1e-9))
+        s = w.sum(dim=1, keepdim=True)
+        w = torch.where(s > 0, w / s, w)                                 # vec / vec.sum() if vec.sum() > 0
+        with phase("D2H"):
+            m0, wh, st = M0[0].cpu().numpy(), w.cpu().numpy(), info[:, 0].cpu().numpy()
+        capped, rejected = int((st == 1).sum()), int((st == 2).sum())
+        if capped or rejected:
+            logger.warning(f"mvo: {capped} of {len(st)} days stopped at max_iter before reaching eps, "
+                           f"{rejected} had a rejected window (NaN / inf factor returns, or a max_weight "
+                           f"below 1 / F; zero weights)")
+        with phase("dense->pandas"):
+            cols = list(_metrics_frame(m0, names).index)
+            pos = [names.index(c) for c in cols]
+            return pd.DataFrame(wh[:, pos], index=pd.Index(proc_dates), columns=cols)
+
+    def prepare_selection(self) -> pd.DataFrame:
+        """factor_selector.py:94-139"""
+        if self.factor_selection is not None:
+            logger.info("Factor selection already prepared. Returning cached result.")
+            return self.factor_selection
+        logger.info("Executing rolling factor selection...")
+        proc_dates = self.dates[self.window:-1]
+        selector_func = FACTOR_SELECTION_METHODS.get(self.method)
+        if selector_func is None:
+            raise ValueError(f"Unknown factor selection method: {self.method}")
+        if not proc_dates:
+            self.factor_selection = pd.DataFrame()
+            return self.factor_selection
+        proc_idx = list(range(self.window, len(self.dates) - 1))
+        if self._mvo_native(selector_func):
+            sel = self._select_mvo_device(proc_dates, proc_idx)
+        else:
+            sel = self._select_general(selector_func, proc_dates, proc_idx)
         selection_df = sel
         selection_df.index.name = "date"
         selection_df.columns.name = "factor"

@@ -299,6 +299,28 @@ fmx_status fmx_ic_window(const double* daily, int64_t F, int64_t D, const int32_
  * order_out [J][F] (rank_IC_IR-descending factor order), w_out [J][F] weights. */
 fmx_status fmx_select_icir_top(const double* metrics, int64_t J, int64_t F, int32_t use_rank_icir,
                                double threshold, int32_t top_x, int32_t* order_out, double* w_out, void* stream);
+/* mvo_selector (factor_selection_methods.py:60-175) for J windows of factor returns.
+ * fret: [D][F] row-major device float64; window j is the rows [d0[j], d1[j]) (device int32).
+ * fmx_mvo_covariance: mu_out [J][F] the window mean, cov_out [J][F][F] the Ledoit-Wolf
+ * constant-correlation shrunk covariance (use_shrinkage) or the ddof=1 sample covariance,
+ * lam_out [J] the shrinkage intensity (0 without shrinkage).  A window with n < 2 rows, bounds
+ * outside [0, D] or a NaN / inf return is rejected: NaN mu / cov / lambda.
+ * fmx_mvo_windows: the exact optimum of
+ *   max_w mu'w - risk_aversion w'Sigma w - turnover_penalty |w - prev|_1,
+ *   sum w = 1, 0 <= w <= min(max_weight, 1)
+ * by ADMM (one workgroup per window).  prev: device [F] or NULL (no turnover term).  w_out
+ * [J][F] (inside the box exactly; not re-normalised), info [J][6] = status (0 converged, 1
+ * max_iter reached, 2 no solution: window rejected or F min(max_weight, 1) < 1, w = 0),
+ * iterations, primal residual max(|x - z|_inf, |sum w - 1|), dual residual, lambda, rho.
+ * 2 <= F <= 256. */
+fmx_status fmx_mvo_covariance(const double* fret, int64_t D, int64_t F, const int32_t* d0_dev, const int32_t* d1_dev,
+                              int64_t J, int32_t use_shrinkage, double* mu_out, double* cov_out, double* lam_out,
+                              void* stream);
+fmx_status fmx_mvo_windows(const double* fret, int64_t D, int64_t F, const int32_t* d0_dev, const int32_t* d1_dev,
+                           int64_t J, double risk_aversion, double max_weight, double turnover_penalty,
+                           const double* prev, int32_t use_shrinkage, int32_t max_iter, double eps, double* w_out,
+                           double* info, void* work, int64_t work_bytes, void* stream);
+int64_t fmx_mvo_windows_work_bytes(int64_t D, int64_t F, int64_t J);
 
 /* ---- factor correlation GEMM (builder-defined) ------------------------ */
 /* Z: per-date z-scored exposures (float64 [F][D][ld], NaN -> 0); M: validity as bf16

@@ -1,6 +1,7 @@
 """Per-kernel timing harness (development tool, not the driver bench).
 
     python tools/kbench.py [--dates D --assets A --factors F] [--ops cs_rank,ic,...] [--reps N]
+    python tools/kbench.py --ops mvo [--mvo-windows J --factors F --mvo-window W] [--reps N]
 
 The panel is generated on the host with numpy (SURVEY 8(d) statistics: N(0,1), 1% NaN,
 5% rounded to one decimal) for a small factor block and tiled along the factor axis on
@@ -134,8 +135,52 @@ OPS = {
 }
 
 
+def _timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(reps):
+        out = fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / reps, out
+
+
+def bench_mvo(J, F, W, reps):
+    """--ops mvo: the rolling MVO selection (engine.mvo_windows) over J windows of W rows of
+    F factor returns, for two (risk_aversion, max_weight, turnover_penalty) settings.  Stage A
+    is timed alone (engine.mvo_covariance), stage B is the whole call minus stage A; the
+    K^-1 rate counts one F x F fp64 read per ADMM iteration."""
+    rng = np.random.default_rng(0)
+    D = J + W
+    R = 0.01 * (0.6 * rng.standard_normal((D, 1)) + rng.standard_normal((D, F)) * rng.uniform(0.3, 2.0, F))
+    R += 0.001 * rng.standard_normal(F)
+    fret = torch.as_tensor(R, device="cuda")
+    prev = torch.as_tensor(rng.dirichlet(np.ones(F)), device="cuda")
+    d0 = np.arange(J, dtype=np.int32)
+    d1 = d0 + np.int32(W)
+    ms_a, _ = _timed(lambda: E.mvo_covariance(fret, d0, d1, True), reps)
+    res = {"stage_a_ms": round(ms_a, 3), "settings": []}
+    print(f"mvo J={J} F={F} W={W}: stage A {ms_a:.3f} ms", flush=True)
+    for gamma, u, tau in ((10.0, 1.0, 0.0), (100.0, 0.05, 5e-4)):
+        ms, (w, info) = _timed(lambda: E.mvo_windows(fret, d0, d1, gamma, u, tau, prev if tau > 0 else None), reps)
+        info = info.cpu().numpy()
+        it = info[:, 1]
+        ms_b = ms - ms_a
+        r = {"gamma": gamma, "max_weight": u, "tau": tau, "total_ms": round(ms, 3), "stage_b_ms": round(ms_b, 3),
+             "iter_mean": round(float(it.mean()), 1), "iter_max": int(it.max()),
+             "not_converged": int((info[:, 0] != 0).sum()),
+             "kinv_GBs": round(float(it.sum()) * F * F * 8 / (ms_b * 1e-3) / 1e9, 1)}
+        res["settings"].append(r)
+        print("   ", r, flush=True)
+    print(json.dumps({"mvo": {"J": J, "F": F, "W": W, **res}}))
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--mvo-windows", type=int, default=2400)
+    p.add_argument("--mvo-window", type=int, default=120)
     p.add_argument("--dates", type=int, default=2520)
     p.add_argument("--assets", type=int, default=5000)
     p.add_argument("--factors", type=int, default=200)
@@ -144,6 +189,8 @@ def main():
     p.add_argument("--phases", action="store_true")
     a = p.parse_args()
     D, A, F = a.dates, a.assets, a.factors
+    if a.ops == "mvo":            # no panel: factor returns only
+        return bench_mvo(a.mvo_windows, F, a.mvo_window, a.reps)
     X, R = panel(D, A, F)
     Y = torch.empty_like(X)
     units = float(D) * A * F
