@@ -1,8 +1,10 @@
 """Loader for the reference's own HOST-ONLY modules (outside the GPU scope):
-the MVO trade-list solvers (portfolio_simulation.py:183-248, :315-746) and
-``mvo_selector`` (factor_selection_methods.py:119-175) when it is called directly or with
-``backend="reference"``, both cvxpy / scipy QPs per date.  ``FactorSelector(method="mvo")``
-itself runs on the device (``engine.mvo_windows``) and never comes here.
+the MVO trade-list solvers (portfolio_simulation.py:183-248, :315-746) for ``mvo_turnover``
+and for ``mvo`` with ``use_cvxpy=False``, ``FMX_SIM_MVO=reference``, no GPU or inputs outside
+the kernel's caps, and ``mvo_selector`` (factor_selection_methods.py:119-175) when it is called
+directly or with ``backend="reference"``: cvxpy / scipy QPs per date.
+``FactorSelector(method="mvo")`` and ``Simulation(method="mvo")`` themselves run on the device
+(``engine.mvo_windows``, ``engine.sim_mvo_books``) and never come here.
 
 They are loaded by file path from ``$FMX_REFERENCE_DIR`` under a private module name.
 The directory is on ``sys.path`` only while the module body executes (its top-level

@@ -959,6 +959,44 @@ def shift_rows(W):
     return out
 
 
+SIM_MVO_MAX_A = 16384
+SIM_MVO_MAX_T = 64
+
+
+def sim_mvo_books(R0, win_rows, win_T, X, present=None, shrinkage=0.1, max_weight=0.03, max_iter=20000, eps=1e-9):
+    """Simulation._daily_trade_list, method 'mvo' (portfolio_simulation.py:183-204, :315-461)
+    for J dates in one launch (fmx_sim_mvo_books): R0 [Dr][A] the zero-filled returns panel,
+    win_rows [J][Lmax] / win_T [J] int32 each date's window rows of R0, X [J][A] the signal,
+    present [J][A] uint8 or None.  Returns (W [J][A] same-day weights: 0 outside the legs, NaN
+    on absent cells; counts [J][2]; info [J][6] = status, iterations, primal residual, dual
+    residual relative to the leg multipliers, delta, rho).  status 0 converged, 1 max_iter reached, 2 x0 fallback, 3 flat day,
+    4 no returns history (the caller supplies the equal-weight book)."""
+    for t, name in ((R0, "R0"), (X, "X")):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != F64 or t.dim() != 2:
+            raise _lib.FmxError(f"sim_mvo_books: {name} must be a float64 2-D HIP device tensor")
+    R0, X = R0.contiguous(), X.contiguous()
+    (Dr, A), J = R0.shape, X.shape[0]
+    if X.shape[1] != A or not 1 <= A <= SIM_MVO_MAX_A:
+        raise _lib.FmxError(f"sim_mvo_books: R0 and X must share 1 <= A <= {SIM_MVO_MAX_A} asset columns")
+    _check_present(present, J, A)
+    win_rows = torch.as_tensor(win_rows, dtype=torch.int32).to(X.device).contiguous()
+    win_T = torch.as_tensor(win_T, dtype=torch.int32).to(X.device).contiguous()
+    if win_rows.dim() != 2 or win_rows.shape[0] != J or tuple(win_T.shape) != (J,):
+        raise _lib.FmxError("sim_mvo_books: win_rows must be [J][Lmax] and win_T [J]")
+    Lmax = int(win_rows.shape[1])
+    if not 1 <= Lmax <= SIM_MVO_MAX_T:
+        raise _lib.FmxError(f"sim_mvo_books: 1 <= Lmax <= {SIM_MVO_MAX_T} window rows supported, got {Lmax}")
+    W = torch.empty((J, A), dtype=F64, device=X.device)
+    counts = torch.empty((J, 2), dtype=F64, device=X.device)
+    info = torch.empty((J, 6), dtype=F64, device=X.device)
+    nb = int(_lib.load().fmx_sim_mvo_books_work_bytes(A, Lmax, J))
+    work, wb = _workspace_bytes(X.device, nb)
+    call("fmx_sim_mvo_books", ptr(R0), int(Dr), int(A), ptr(win_rows), ptr(win_T), Lmax, ptr(X), ptr(present), int(J),
+         float(shrinkage), float(max_weight), int(max_iter), float(eps), ptr(W), ptr(counts), ptr(info), ptr(work), wb,
+         stream_ptr())
+    return W, counts, info
+
+
 def mm_combine(Wf, counts, fw, colmap, wdate):
     """multi_manager combination (multi_manager.py:51-72) of fmx_trade_equal outputs."""
     F, D, A = Wf.shape

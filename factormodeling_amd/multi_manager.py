@@ -6,9 +6,10 @@ Simulation._daily_trade_list over ``factors_df[fac].dropna()`` with the settings
 NaN cells = no row), and each weight date folds the managers' books and counts in
 ``factor_weights`` column order (``k_mm_combine``).  Returns the reference's
 ``(final_weights, final_counts)``: nonzero weights over ``(date, symbol)``, counts indexed
-by date.  'mvo' / 'mvo_turnover' managers (a host QP per date) take their books from
-``compute_manager_weights`` -- the drop-in ``Simulation._daily_trade_list``, which hands
-them to the reference's own solvers -- and fold on the device like the others.  Columns
+by date.  'mvo' / 'mvo_turnover' managers (a QP per date) take their books from
+``compute_manager_weights`` -- the drop-in ``Simulation._daily_trade_list``, which solves
+'mvo' on the device one manager at a time and hands 'mvo_turnover' (and 'mvo' with
+``use_cvxpy=False``) to the reference's own solvers -- and fold on the device like the others.  Columns
 absent from ``factors_df`` log the reference's warning (:42-44).  Symbol order within a date: ``daily_weights.add(mgr_w_today * fac_w,
 fill_value=0)`` (:63) aligns the first-appearance ``all_symbols`` index with a manager's
 date-sorted book index; unless the two are identical pandas returns their sorted union,

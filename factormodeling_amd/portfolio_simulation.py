@@ -8,13 +8,19 @@ the GPU through libfmx:
 * ``_daily_trade_list`` (:96-154): methods 'equal' (``k_trade_equal``, :156-170) and
   'linear' (``k_trade_linear``: normalised legs + cap-and-redistribute, :172-181,
   :250-313), then the per-symbol ``shift(1)``;
+* ``_daily_trade_list`` for 'mvo' (:183-204, :315-461): every date's minimum-variance QP in
+  one launch (``k_sim_mvo``, ``simulation.mvo_trade_list``), solved to its optimum; the
+  reference's cvxpy call stops at eps 1e-4, so its weights differ in the digits that
+  tolerance leaves open;
 * ``_daily_portfolio_returns`` (:748-797): long / short P&L, turnover and the cap-flag
   transaction cost per date (``k_pnl_daily``) and the per-symbol contributions
   (``k_pnl_contrib``);
 * ``_calculate_metrics`` (:799-819): the daily IC (``k_daily_corr``).
 
-The MVO methods ('mvo', 'mvo_turnover', :183-248, :315-746) solve a cvxpy / scipy QP per
-date on the host and stay the reference's own code: ``_daily_trade_list`` hands them to the
+'mvo_turnover' (:227-248, :463-746) chains each day's QP to the previous day's solution and
+stays the reference's own host code, as does 'mvo' with ``use_cvxpy=False`` (an explicit
+request for the scipy SLSQP solver), with ``FMX_SIM_MVO=reference`` in the environment,
+without a GPU or outside the kernel's caps: ``_daily_trade_list`` hands these to the
 reference's ``Simulation``, loaded by file path from ``FMX_REFERENCE_DIR`` (the user's
 reference checkout; a module of the same name cannot sit on ``sys.path`` next to this
 drop-in), while the P&L and metrics of the resulting weights still run on the device.
@@ -23,6 +29,8 @@ from ``portfolio_analyzer`` when ``run()`` needs it.
 """
 from __future__ import annotations
 
+import logging
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -32,7 +40,7 @@ import torch
 from . import _refload
 from . import engine as E
 from .panel import device
-from .simulation import daily_trade_list
+from .simulation import daily_trade_list, mvo_trade_list
 
 RESULT_COLS = ["log_return", "long_return", "short_return", "long_turnover", "short_turnover", "turnover"]
 
@@ -158,12 +166,49 @@ class Simulation:
 
     # ----------------------------------------------------------------------------- trade list
     def _daily_trade_list(self):
-        """portfolio_simulation.py:96-154 (equal / linear on the device)."""
+        """portfolio_simulation.py:96-154 (equal / linear / mvo on the device)."""
+        if self.method == "mvo" and self._mvo_runs_natively():
+            return self._native_mvo_trade_list()
         if self.method in ("mvo", "mvo_turnover"):
             return self._host_trade_list()
         if self.method not in ("equal", "linear"):
             raise ValueError(f"Unknown method {self.method}")
         return daily_trade_list(self.custom_feature, self.pct, self.method, self.max_weight)
+
+    def _mvo_runs_natively(self) -> bool:
+        """'mvo' solves every date's QP on the device unless the caller asked for the host
+        SLSQP solver (``use_cvxpy=False``) or the reference (``FMX_SIM_MVO=reference``), no
+        GPU is visible, or the inputs are outside the kernel's caps (more than 16,384
+        symbols, a lookback outside 1..64, a shrinkage intensity above 1) or not two unique
+        (date, symbol) indexes.  ``mvo_solver`` only selects among cvxpy back ends for the
+        same QP and is ignored."""
+        if not self.use_cvxpy or os.environ.get("FMX_SIM_MVO", "").lower() == "reference":
+            return False
+        if not torch.cuda.is_available():
+            return False
+        f, r = self.custom_feature, self.returns
+        if not (isinstance(f, pd.Series) and isinstance(r, pd.Series)):
+            return False
+        for idx in (f.index, r.index):
+            if not isinstance(idx, pd.MultiIndex) or idx.nlevels != 2 or not idx.is_unique:
+                return False
+        if not 1 <= int(self.lookback_period) <= E.SIM_MVO_MAX_T or not self.shrinkage_intensity <= 1.0:
+            return False
+        return f.index.get_level_values(1).nunique() <= E.SIM_MVO_MAX_A
+
+    def _native_mvo_trade_list(self):
+        """portfolio_simulation.py:96-154 with :183-204, :315-461 (``simulation.mvo_trade_list``);
+        days the solver left unconverged or answered with the x0 fallback are reported once."""
+        shifted, counts, extra = mvo_trade_list(self.custom_feature, self.returns, self.pct, self.max_weight,
+                                                int(self.lookback_period), float(self.shrinkage_intensity),
+                                                return_info=True)
+        info = extra["info"]
+        n1, n2 = int((info[:, 0] == 1).sum()), int((info[:, 0] == 2).sum())
+        if n1 or n2:
+            logging.getLogger("portfolio_simulation").warning(
+                "mvo: of %d days, %d stopped at the iteration limit (last iterate kept) and %d took the "
+                "equal-leg fallback x0 (one-row window or max_weight too small for a leg)", len(info), n1, n2)
+        return shifted, counts
 
     def _host_trade_list(self):
         """'mvo' / 'mvo_turnover': the reference's own per-date QP loop

@@ -5,8 +5,15 @@ returns for ``method='equal'`` (portfolio_simulation.py:96-170): the per-symbol
 ``shift(1)`` of each day's equal-weight long/short book (a Series over the sorted
 ``(date, symbol)`` rows of ``custom_feature``) and the ``long_count`` / ``short_count``
 DataFrame indexed by date.  Computed by ``k_trade_equal`` / ``k_trade_linear`` (normalised
-legs + cap-and-redistribute, :172-181, :250-313) and the per-symbol shift (csrc/sim.hip);
-the MVO methods are host QPs (cvxpy) and stay with the reference.
+legs + cap-and-redistribute, :172-181, :250-313) and the per-symbol shift (csrc/sim.hip).
+
+``mvo_trade_list(custom_feature, returns, ...)`` returns the same pair for ``method='mvo'``
+(:183-204, :315-461): ``mvo_window_rows`` lists each date's returns window (the last
+``lookback_period`` distinct returns dates before it on which one of the day's symbols has a
+row), ``k_sim_mvo`` (csrc/sim_mvo.hip) solves every date's minimum-variance QP in one launch,
+and days without any returns history take the equal-weight book (:188-190).
+``method='mvo_turnover'`` chains each day to the previous day's solution and stays the
+reference's host QP loop.
 """
 from __future__ import annotations
 
@@ -71,4 +78,97 @@ def daily_trade_list(custom_feature: pd.Series, pct: float = 0.1, method: str = 
     counts_df = pd.DataFrame({"long_count": counts[:, 0].astype(np.int64),
                               "short_count": counts[:, 1].astype(np.int64)},
                              index=pd.Index(pi.dates, name=custom_feature.index.names[0]))
+    return shifted, counts_df
+
+
+def _levels(index: pd.MultiIndex):
+    names = list(index.names)
+    return (index.get_level_values("date" if "date" in names else 0),
+            index.get_level_values("symbol" if "symbol" in names else 1))
+
+
+def _returns_grid(pi, returns):
+    """The returns' rows on the feature's symbol columns: (sorted distinct returns dates,
+    row date codes, row symbol columns, keep mask) -- rows of other symbols are dropped."""
+    index = returns.index if isinstance(returns, (pd.Series, pd.DataFrame)) else returns
+    dl, sl = _levels(index)
+    rd, rdates = pd.factorize(dl, sort=True)
+    rs = pi.symbols.get_indexer(sl)
+    return np.asarray(rdates), rd.astype(np.int64), rs.astype(np.int64), rs >= 0
+
+
+def mvo_window_rows(feature_index, returns, lookback: int, device=None):
+    """Each feature date's returns window (portfolio_simulation.py:319-334) as rows of the
+    sorted distinct returns dates: (win_rows int32 [J][Lmax], win_T int32 [J]), ascending
+    inside a window, Lmax = min(lookback, number of returns dates) (at least 1).  A returns
+    date belongs to date d's candidates when it is < d and one of d's symbols has a returns
+    row on it (NaN values included) -- a presence product [J][A] x [A][Dr]; the window is the
+    last ``lookback`` candidates, so on a ragged panel it is not a contiguous date range.
+    ``feature_index`` is the feature's (date, symbol) MultiIndex (or its PanelIndex),
+    ``returns`` the returns Series or its index.  torch ops only: runs on any device."""
+    pi = feature_index if hasattr(feature_index, "present_np") else panel_index(feature_index)
+    rdates, rd, rs, keep = _returns_grid(pi, returns)
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+    J, A, Dr = pi.D, pi.A, len(rdates)
+    L = max(1, min(int(lookback), Dr))
+    if Dr == 0:
+        return (torch.zeros((J, L), dtype=torch.int32, device=dev), torch.zeros((J,), dtype=torch.int32, device=dev))
+    rp = np.zeros((Dr, A), dtype=np.float32)
+    rp[rd[keep], rs[keep]] = 1.0
+    fp = np.ones((J, A), dtype=np.float32) if pi.present_np is None else pi.present_np.astype(np.float32)
+    hit = (torch.as_tensor(fp, device=dev) @ torch.as_tensor(rp, device=dev).T) > 0.5          # [J][Dr]
+    nbefore = np.searchsorted(rdates, np.asarray(pi.dates), side="left")                      # returns dates < d
+    hit &= torch.arange(Dr, device=dev)[None, :] < torch.as_tensor(nbefore, device=dev)[:, None]
+    after = hit.flip(1).cumsum(1).flip(1)                 # candidates at or after each position
+    sel = hit & (after <= L)
+    win_T = sel.sum(1)
+    jj, rr = sel.nonzero(as_tuple=True)
+    win_rows = torch.zeros((J, L), dtype=torch.int32, device=dev)
+    win_rows[jj, win_T[jj] - after[jj, rr]] = rr.to(torch.int32)
+    return win_rows, win_T.to(torch.int32)
+
+
+def _series_out(pi, custom_feature, W, counts):
+    """(shifted Series over the sorted (date, symbol) rows, counts DataFrame by date)."""
+    W = W.cpu().numpy().reshape(-1)
+    counts = counts.cpu().numpy()
+    order = np.sort(pi.flat)
+    d, s = order // pi.A, order % pi.A
+    index = pd.MultiIndex.from_arrays([pi.dates[d], pi.symbols[s]], names=list(custom_feature.index.names))
+    shifted = pd.Series(W[order], index=index)
+    counts_df = pd.DataFrame({"long_count": counts[:, 0].astype(np.int64),
+                              "short_count": counts[:, 1].astype(np.int64)},
+                             index=pd.Index(pi.dates, name=custom_feature.index.names[0]))
+    return shifted, counts_df
+
+
+def mvo_trade_list(custom_feature: pd.Series, returns: pd.Series, pct: float = 0.1, max_weight: float = 0.03,
+                   lookback_period: int = 60, shrinkage_intensity: float = 0.1, max_iter: int = 20000,
+                   eps: float = 1e-9, return_info: bool = False):
+    """``Simulation._daily_trade_list()`` for ``method='mvo'`` on the device: the same
+    ``(shifted, counts_df)`` pair as ``daily_trade_list``.  Every date's QP is solved to its
+    optimum (engine.sim_mvo_books); days without returns history carry the equal-weight book.
+    With ``return_info`` a third value holds the solver's ``info`` [D][6], the same-day
+    ``books`` [D][A] (NaN where the feature has no row) and their ``dates`` / ``symbols``."""
+    custom_feature = by_date(custom_feature)
+    pi = panel_index(custom_feature.index)
+    dev = device()
+    rdates, rd, rs, keep = _returns_grid(pi, returns)
+    r0 = np.zeros((max(len(rdates), 1), pi.A))
+    rv = returns.to_numpy(dtype=np.float64, na_value=np.nan)[keep]
+    r0[rd[keep], rs[keep]] = np.where(np.isnan(rv), 0.0, rv)                                  # fillna(0), :337
+    win_rows, win_T = mvo_window_rows(pi, returns, lookback_period, device=dev)
+    X = torch.as_tensor(pi.to_dense(custom_feature.to_numpy(dtype=np.float64)), device=dev)      # [1][D][A]
+    present = pi.present(dev)
+    W, counts, info = E.sim_mvo_books(torch.as_tensor(r0, device=dev), win_rows, win_T, X[0], present,
+                                      shrinkage_intensity, max_weight, max_iter, eps)
+    eq = info[:, 0] == 4
+    if bool(eq.any()):
+        _, ce, we = E.trade_books(X, "equal", pct, max_weight, present=present, nan_absent=False, raw=True)
+        W[eq] = we[0][eq]
+        counts[eq] = ce[0][eq]
+    shifted, counts_df = _series_out(pi, custom_feature, E.shift_rows(W)[0], counts)
+    if return_info:
+        return shifted, counts_df, {"info": info.cpu().numpy(), "books": W.cpu().numpy(), "dates": pi.dates,
+                                    "symbols": pi.symbols}
     return shifted, counts_df

@@ -480,6 +480,35 @@ fmx_status fmx_shift_rows(const double* W, double* out, int64_t F, int64_t D, in
 fmx_status fmx_mm_combine(const double* Wf, const double* counts, const double* fw, const int32_t* colmap,
                           const int32_t* wdate, double* out, double* out_counts, int64_t Fw, int64_t Dw,
                           int64_t D, int64_t A, void* stream);
+/* Method 'mvo' (portfolio_simulation.py:96-154, :183-204, :315-461): the same-day minimum-
+ * variance books of J dates in one launch, one workgroup per date (csrc/sim_mvo.hip).
+ *   R0 [Dr][A]: the returns panel, missing cells and NaN as 0 (unstack().fillna(0), :337);
+ *   win_rows [J][Lmax], win_T [J] (device int32): date j's window is the rows
+ *     win_rows[j][0 .. win_T[j]) of R0 -- the last lookback_period distinct returns dates
+ *     before it on which one of its symbols has a row (:319-334); 1 <= Lmax <= 64;
+ *   X [J][A] the signal, present [J][A] (or NULL: every cell is a row).
+ * Per date: Sigma = (1 - s) (cov(ddof=1) + 1e-6 I) + s avg_var I with avg_var the mean
+ * diagonal over the PRESENT symbols (:349-374; s = shrinkage <= 0: no shrinkage), then
+ *   min w'Sigma w,  sum_{x>0} w = 1, sum_{x<0} w = -1, 0 <= w <= u on x > 0,
+ *   -u <= w <= 0 on x < 0, w = 0 elsewhere                      (u = max_weight, :376-421)
+ * by ADMM with a Woodbury x-step (Sigma = delta I + low rank).  W [J][A]: the weights, 0 on
+ * present cells outside the legs, NaN on absent cells (the layout fmx_shift_rows takes);
+ * counts [J][2] = (long_count, short_count); info [J][6] = status, iterations, primal
+ * residual max(|x - z|_inf, leg-sum errors), dual residual rho |z - z_prev|_inf relative to the
+ * larger leg multiplier (the gradient's size), delta, rho.  status: 0 converged (|x - z|_inf
+ * <= eps, leg sums within eps / 10, relative dual residual <= eps), 1 max_iter reached
+ * (last iterate, inside the box exactly), 2 the x0 fallback +1/n_pos, -1/n_neg (:388-390,
+ * :451-459: T = 1, u n_pos < 1 or u n_neg < 1, non-finite window), 3 flat day (a leg empty or
+ * fewer than 2 rows, :109-126: zeros, counts 0), 4 no returns history (win_T = 0, :188-190:
+ * the caller supplies the equal-weight book; zeros, counts 0).  A row index outside [0, Dr)
+ * or win_T outside [0, Lmax] is FMX_ERR_ARG (the lists are read back before the launch).
+ * A <= 16384.  work: fmx_sim_mvo_books_work_bytes(A, Lmax, J) bytes (0 unless the A-vector
+ * and the Lmax x Lmax matrix exceed the LDS together). */
+int64_t fmx_sim_mvo_books_work_bytes(int64_t A, int64_t Lmax, int64_t J);
+fmx_status fmx_sim_mvo_books(const double* R0, int64_t Dr, int64_t A, const int32_t* win_rows, const int32_t* win_T,
+                             int64_t Lmax, const double* X, const uint8_t* present, int64_t J, double shrinkage,
+                             double max_weight, int32_t max_iter, double eps, double* W, double* counts,
+                             double* info, void* work, int64_t work_bytes, void* stream);
 
 /* ---- portfolio P&L (portfolio_simulation.py:748-819) ---------- */
 /* Replaces Simulation._daily_portfolio_returns' per-date sums on the aligned [D][A] grid

@@ -2,6 +2,7 @@
 
     python tools/kbench.py [--dates D --assets A --factors F] [--ops cs_rank,ic,...] [--reps N]
     python tools/kbench.py --ops mvo [--mvo-windows J --factors F --mvo-window W] [--reps N]
+    python tools/kbench.py --ops sim_mvo [--dates D --assets A --lookback L --max-weight U] [--reps N]
 
 The panel is generated on the host with numpy (SURVEY 8(d) statistics: N(0,1), 1% NaN,
 5% rounded to one decimal) for a small factor block and tiled along the factor axis on
@@ -177,8 +178,40 @@ def bench_mvo(J, F, W, reps):
     print(json.dumps({"mvo": {"J": J, "F": F, "W": W, **res}}))
 
 
+def bench_sim_mvo(D, A, lookback, u, reps):
+    """--ops sim_mvo: the simulator's MVO trade list (engine.sim_mvo_books) for D dates of A
+    assets, every date's window the `lookback` returns rows before it (dates 0 and 1 take the
+    equal-weight / x0 exits).  Reports ms per call and the histogram of ADMM iterations; the
+    panel rate counts the 2 T A fp64 panel reads of one iteration."""
+    rng = np.random.default_rng(0)
+    R = 0.01 * (0.6 * rng.standard_normal((D, 1)) + rng.standard_normal((D, A)) * rng.uniform(0.3, 2.0, A))
+    X = rng.standard_normal((D, A))
+    X[rng.random((D, A)) < 0.05] = 0.0
+    T = np.minimum(np.arange(D), lookback).astype(np.int32)
+    L = min(lookback, max(D - 1, 1))
+    rows = np.zeros((D, L), dtype=np.int32)
+    for j in range(D):
+        rows[j, :T[j]] = np.arange(j - T[j], j)
+    R0, Xd = torch.as_tensor(R, device="cuda"), torch.as_tensor(X, device="cuda")
+    rows_d, T_d = torch.as_tensor(rows, device="cuda"), torch.as_tensor(T, device="cuda")
+    ms, (W, counts, info) = _timed(lambda: E.sim_mvo_books(R0, rows_d, T_d, Xd, None, 0.1, u), reps)
+    info = info.cpu().numpy()
+    qp = info[:, 0] <= 1
+    it = info[qp, 1]
+    edges = [0, 10, 20, 30, 40, 60, 80, 120, 200, 500, 20000]
+    hist = {f"<={b}": int(((it > a) & (it <= b)).sum()) for a, b in zip(edges[:-1], edges[1:])}
+    reads = float((it * T[qp]).sum()) * 2 * A * 8
+    res = {"D": D, "A": A, "lookback": lookback, "max_weight": u, "ms": round(ms, 3),
+           "status_counts": {int(k): int((info[:, 0] == k).sum()) for k in np.unique(info[:, 0])},
+           "iter_mean": round(float(it.mean()), 1), "iter_max": int(it.max()), "iter_hist": hist,
+           "panel_GBs": round(reads / (ms * 1e-3) / 1e9, 1)}
+    print(json.dumps({"sim_mvo": res}))
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--lookback", type=int, default=60)
+    p.add_argument("--max-weight", type=float, default=0.03)
     p.add_argument("--mvo-windows", type=int, default=2400)
     p.add_argument("--mvo-window", type=int, default=120)
     p.add_argument("--dates", type=int, default=2520)
@@ -191,6 +224,8 @@ def main():
     D, A, F = a.dates, a.assets, a.factors
     if a.ops == "mvo":            # no panel: factor returns only
         return bench_mvo(a.mvo_windows, F, a.mvo_window, a.reps)
+    if a.ops == "sim_mvo":        # signal + returns panels only
+        return bench_sim_mvo(D, A, a.lookback, a.max_weight, a.reps)
     X, R = panel(D, A, F)
     Y = torch.empty_like(X)
     units = float(D) * A * F
