@@ -5,8 +5,18 @@
 ``composite_factor`` on ``factors_df.index``); the per-date percentiles, suffix scaling,
 prefix-group proxies, z-score / rank normalisation, weighting and demeaning run in the
 gfx950 kernels of ``csrc/composite.hip`` and ``csrc/cs_ops.hip``.  The two plotting helpers
-the notebook imports (pipeline.ipynb:55) are host-side matplotlib code, as in the
+the notebook imports (pipeline.ipynb:55) draw with host-side matplotlib, as in the
 reference.
+
+``quantile_backtest_log`` returns the numbers ``plot_quantile_backtests_log`` (:47-134)
+draws: per factor column, the mean return of every per-date quantile bucket, the buckets
+lagged one row per symbol.  The reference computes them with one ``pd.qcut`` call per date
+(:63-98); here the bucket labels (``fmx_cs_qlabel``: ordinal ranks and the qcut label from a
+host table of pandas' own cut points) and the bucket means (``fmx_qbucket_mean``: exact
+sums) run in ``csrc/qbacktest.hip`` on the union grid of the two indexes, the factor
+columns uploaded in chunks of at most ``QBACKTEST_DEVICE_BUDGET`` bytes.  Inputs the
+kernels do not take (more than 32 groups or 8,192 symbols, rows of a date not in sorted
+symbol order, no GPU) keep the reference's pandas loop, ``_quantile_backtest_host``.
 """
 from __future__ import annotations
 
@@ -164,26 +174,174 @@ def plot_factor_distributions(factors_df: pd.DataFrame, exclude: list = None, bi
     plt.show()
 
 
+# ----------------------------------------------------------------------------- quantile backtest
+# Device bytes one chunk of factor columns may take in quantile_backtest_log.  Per cell: the
+# fp64 panel (8), on a ragged grid the uploaded rows it is scattered from, alive with it (up to
+# 8), the valid-cell mask of the count pass (1) and the label byte (1).  The per-row counts and
+# the [F][D][n] means are not per cell and are left out.
+QBACKTEST_DEVICE_BUDGET = 1 << 30
+_QB_CELL_BYTES = 18
+
+
+def _quantile_backtest_host(feature: pd.Series, returns: pd.Series, n_groups: int) -> pd.DataFrame:
+    """composite_factor.py:63-98, restated: one ``pd.qcut`` call per date on the host."""
+    lbl = feature.groupby(level="date").transform(
+        lambda x: pd.qcut(x.rank(method="first"), n_groups, labels=False, duplicates="drop"))
+    q = (n_groups - lbl).astype("Int64").groupby(level="symbol").shift(1)
+    df = pd.DataFrame({"log_ret": returns, "group": q}).dropna(subset=["group", "log_ret"])
+    g = df.reset_index().groupby(["date", "group"])["log_ret"].mean().unstack(level="group").sort_index()
+    return g.reindex(columns=range(1, n_groups + 1))
+
+
+class _QbPlan:
+    """The union (date, symbol) grid of the factor frame's and the returns' indexes (what the
+    reference's outer join aligns on; portfolio_simulation._Grid does the same), the feature
+    rows' cells on it, the previous-row table and the dense returns panel."""
+
+    def __init__(self, findex: pd.MultiIndex, returns: pd.Series):
+        rindex = returns.index
+        fd, fs = findex.get_level_values(0), findex.get_level_values(1)
+        rd, rs = rindex.get_level_values(0), rindex.get_level_values(1)
+        self.dates = fd.unique().union(rd.unique()).sort_values()
+        self.symbols = fs.unique().union(rs.unique()).sort_values()
+        self.D, self.A = len(self.dates), len(self.symbols)
+        D, A = self.D, self.A
+        self.flat = self.dates.get_indexer(fd).astype(np.int64) * A + self.symbols.get_indexer(fs)
+        self.dense = len(findex) == D * A and bool(np.all(self.flat == np.arange(D * A)))
+        self.present = self.prev_row = None
+        if not self.dense:
+            pres = np.zeros(D * A, dtype=bool)
+            pres[self.flat] = True
+            pres = pres.reshape(D, A)
+            # previous feature row of the symbol: its rows are in date order (PanelIndex), so
+            # the previous row in index order is the latest earlier date on which it has one
+            at = np.where(pres, np.arange(D, dtype=np.int32)[:, None], np.int32(-1))
+            last = np.maximum.accumulate(at, axis=0)
+            prev = np.vstack([np.full((1, A), -1, np.int32), last[:-1]]) if D else at
+            prev[~pres] = -1
+            self.present = pres.astype(np.uint8)
+            self.prev_row = np.ascontiguousarray(prev, dtype=np.int32)
+        R = np.full(D * A, np.nan)
+        R[self.dates.get_indexer(rd).astype(np.int64) * A + self.symbols.get_indexer(rs)] = \
+            returns.to_numpy(dtype=np.float64, na_value=np.nan)
+        self.R = R.reshape(D, A)
+
+
+def _qb_device_reason(com_factors_df, returns, n_groups):
+    """None when the device path can take the input, else why not."""
+    if not (isinstance(n_groups, (int, np.integer)) and 2 <= n_groups <= engine.QLABEL_MAX_GROUPS):
+        return f"n_groups must be an integer in [2, {engine.QLABEL_MAX_GROUPS}]"
+    if not isinstance(returns, pd.Series):
+        return "returns must be a Series"
+    for name, idx in (("com_factors_df", com_factors_df.index), ("returns", returns.index)):
+        if not isinstance(idx, pd.MultiIndex) or idx.nlevels != 2 or list(idx.names) != ["date", "symbol"]:
+            return f"{name} needs a two-level (date, symbol) MultiIndex"
+        if not idx.is_unique:
+            return f"{name} has duplicate (date, symbol) rows"
+    if com_factors_df.columns.has_duplicates:
+        return "duplicate factor columns"
+    with np.errstate(invalid="ignore"):
+        if (np.abs(returns.to_numpy(dtype=np.float64, na_value=np.nan)) >= 2.0 ** 79).any():
+            return "infinite (or >= 2^79) returns do not fit the exact fixed-point sums"
+    try:
+        P = panel_index(com_factors_df.index)
+    except ValueError as e:
+        return str(e)
+    if not P.row_layout()[2]:
+        return "the rows of a date are not in sorted-symbol order (rank 'first' ties go by row order)"
+    try:
+        nsym = len(com_factors_df.index.get_level_values(1).unique().union(returns.index.get_level_values(1).unique()))
+    except TypeError as e:
+        return f"symbols of the two indexes do not sort together: {e}"
+    if nsym > engine.QLABEL_MAX_A:
+        return f"{nsym} symbols exceed the label kernel's {engine.QLABEL_MAX_A}-asset rows"
+    return None
+
+
+def _quantile_backtest_device(com_factors_df, returns, n_groups):
+    n = int(n_groups)
+    cols = list(com_factors_df.columns)
+    dev = device()
+    with phase("host plan"):
+        plan = _QbPlan(com_factors_df.index, returns)
+    D, A = plan.D, plan.A
+    Rd = torch.as_tensor(plan.R, device=dev)
+    prev = torch.as_tensor(plan.prev_row, device=dev) if plan.prev_row is not None else None
+    pres = torch.as_tensor(plan.present, device=dev) if plan.present is not None else None
+    flat = torch.as_tensor(plan.flat, device=dev) if not plan.dense else None
+    step = max(1, int(QBACKTEST_DEVICE_BUDGET // max(1, _QB_CELL_BYTES * D * A)))
+    means, counts = [], []
+    for c0 in range(0, len(cols), step):
+        with phase("pandas->dense"):
+            v = com_factors_df.iloc[:, c0:c0 + step].to_numpy(dtype=np.float64, na_value=np.nan)
+            host = np.ascontiguousarray(v.T)
+        with phase("H2D"):
+            t = torch.as_tensor(host, device=dev)
+        if plan.dense:
+            X = t.reshape(-1, D, A)
+        else:
+            X = torch.full((t.shape[0], D * A), float("nan"), dtype=torch.float64, device=dev)
+            X[:, flat] = t
+            X = X.reshape(-1, D, A)
+        labels = engine.cs_qlabel(X, n, pres)
+        del X, t
+        m, c = engine.qbucket_mean(labels, Rd, n, prev_row=prev)
+        del labels
+        means.append(m)
+        counts.append(c)
+    if not cols:
+        return {}
+    with phase("D2H"):
+        mean = torch.cat(means).cpu().numpy()
+        count = torch.cat(counts).cpu().numpy()
+    columns = pd.Index(np.arange(1, n + 1, dtype=np.int64), name="group")
+    out = {}
+    for k, col in enumerate(cols):
+        keep = count[k].sum(axis=1) > 0
+        out[col] = pd.DataFrame(mean[k][keep], index=plan.dates[keep].rename("date"), columns=columns)
+    return out
+
+
+def quantile_backtest_log(com_factors_df: pd.DataFrame, returns: pd.Series, n_groups: int = 5,
+                          backend: str = "auto") -> dict:
+    """The numbers behind ``plot_quantile_backtests_log``: for every column of
+    ``com_factors_df`` the frame the reference's inner ``quantile_backtest_log``
+    (composite_factor.py:63-98) computes -- index the sorted dates that have a kept cell
+    (named ``date``), columns the groups 1..n_groups (int64, named ``group``, 1 = top),
+    values the mean log return of the group, NaN for an empty one.
+
+    ``backend``: ``"host"`` is the reference's pandas loop; ``"device"`` the gfx950 kernels of
+    ``csrc/qbacktest.hip`` (raises when they cannot take the input); ``"auto"`` the device
+    when a GPU is visible, 2 <= n_groups <= 32, both indexes are unique two-level
+    (date, symbol) MultiIndexes, every date's rows are in sorted-symbol order and the union
+    grid has at most 8,192 symbols -- otherwise the host loop."""
+    if backend not in ("auto", "host", "device"):
+        raise ValueError("backend must be 'auto', 'host' or 'device'")
+    if backend != "host":
+        reason = _qb_device_reason(com_factors_df, returns, n_groups)
+        if backend == "device":
+            if reason is not None:
+                raise ValueError(f"quantile_backtest_log: the device path cannot take this input: {reason}")
+            return _quantile_backtest_device(com_factors_df, returns, n_groups)
+        if reason is None and torch.cuda.is_available():
+            return _quantile_backtest_device(com_factors_df, returns, n_groups)
+    return {c: _quantile_backtest_host(com_factors_df[c], returns, n_groups) for c in com_factors_df.columns}
+
+
 def plot_quantile_backtests_log(com_factors_df: pd.DataFrame, returns: pd.Series, n_groups: int = 5, ncols: int = 2,
                                 figsize: tuple = (20, 6)):
     """composite_factor.py:47-134 -- per-date quantile buckets (1 = top), lagged one row
-    per symbol, mean log return per bucket, cumulative P&L and the L1-S{n} spread."""
+    per symbol, mean log return per bucket, cumulative P&L and the L1-S{n} spread.  The
+    bucket means of all columns come from one ``quantile_backtest_log`` call."""
     import matplotlib.pyplot as plt
 
-    def buckets(feature: pd.Series) -> pd.DataFrame:
-        lbl = feature.groupby(level="date").transform(
-            lambda x: pd.qcut(x.rank(method="first"), n_groups, labels=False, duplicates="drop"))
-        q = (n_groups - lbl).astype("Int64").groupby(level="symbol").shift(1)
-        df = pd.DataFrame({"log_ret": returns, "group": q}).dropna(subset=["group", "log_ret"])
-        g = df.reset_index().groupby(["date", "group"])["log_ret"].mean().unstack(level="group").sort_index()
-        return g.reindex(columns=range(1, n_groups + 1))
-
+    frames = quantile_backtest_log(com_factors_df, returns, n_groups, backend="auto")
     facs = list(com_factors_df.columns)
     nrows = max(1, math.ceil(len(facs) / ncols))
     fig, axes = plt.subplots(nrows, ncols, figsize=(figsize[0], figsize[1] * nrows), squeeze=False)
     for i, fac in enumerate(facs):
         ax = axes[i // ncols][i % ncols]
-        g = buckets(com_factors_df[fac])
+        g = frames[fac]
         cum = np.expm1(g.cumsum())
         cum[f"DN_L1-S{n_groups}"] = np.expm1((g[1] - g[n_groups]).cumsum())
         for line in cum.columns:

@@ -1053,3 +1053,90 @@ def daily_corr(X, R):
     out = torch.empty((D, 2), dtype=F64, device=X.device)
     call("fmx_daily_corr", ptr(X), ptr(R), ptr(out), D, A, stream_ptr())
     return out
+
+
+# ----------------------------------------------------------------------------- quantile backtest
+QLABEL_MAX_A = 8192         # fmx_cs_qlabel / fmx_qbucket_mean: one row's (key, asset) pairs in LDS
+QLABEL_MAX_GROUPS = 32
+_QCUT: dict = {}            # n_groups -> {m: cum row}
+
+
+def qcut_cum(m: int, n_groups: int) -> np.ndarray:
+    """cum[k] = number of ordinal ranks 1..m whose label under
+    ``pd.qcut(ranks, n_groups, labels=False, duplicates="drop")`` is <= k (int32 [n_groups];
+    composite_factor.py:71-74).  qcut's bins are ``Series(ranks).quantile(linspace(0, 1,
+    n + 1))`` and a rank r gets the first bin whose right edge is >= r, so cum[k] is the
+    floor of pandas' own (k + 1)-th edge -- taken from pandas, because the floating-point
+    edges do not follow a closed form.  m <= 1: all zero (qcut labels nothing).  Cached."""
+    import pandas as pd
+    tab = _QCUT.setdefault(int(n_groups), {})
+    row = tab.get(int(m))
+    if row is None:
+        if m <= 1:
+            row = np.zeros(n_groups, dtype=np.int32)
+        else:
+            edges = pd.Series(np.arange(1.0, m + 1)).quantile(np.linspace(0, 1, n_groups + 1)).to_numpy()
+            row = np.floor(edges[1:]).astype(np.int32)
+        row.setflags(write=False)
+        tab[int(m)] = row
+    return row
+
+
+def cs_qlabel(X, n_groups: int, present=None):
+    """Per-date quantile groups (fmx_cs_qlabel): uint8 [F][D][A], 0 = none (absent, NaN or a
+    date of <= 1 valid cells), else ``n_groups - qcut label`` of the cell's
+    rank(method="first") (1 = top; composite_factor.py:71-77).  The cut table holds the
+    distinct valid-cell counts of the panel's rows (one device count pass)."""
+    X = as3(X)
+    _check_panel(X)
+    F, D, A = X.shape
+    _check_present(present, D, A)
+    n = int(n_groups)
+    if not 2 <= n <= QLABEL_MAX_GROUPS:
+        raise _lib.FmxError(f"cs_qlabel: 2 <= n_groups <= {QLABEL_MAX_GROUPS}, got {n_groups}")
+    if A > QLABEL_MAX_A:
+        raise _lib.FmxError(f"cs_qlabel: rows of A <= {QLABEL_MAX_A} assets, got {A}")
+    labels = torch.empty((F, D, A), dtype=torch.uint8, device=X.device)
+    if labels.numel() == 0:
+        return labels
+    valid = ~torch.isnan(X)
+    if present is not None:
+        valid &= present.unsqueeze(0) != 0
+    ms = torch.unique(valid.sum(dim=2)).cpu().numpy()
+    del valid
+    ms = [int(m) for m in ms if m >= 2]
+    m_index = np.full(A + 1, -1, dtype=np.int32)
+    m_index[ms] = np.arange(len(ms), dtype=np.int32)
+    cum = np.stack([qcut_cum(m, n) for m in ms]) if ms else np.zeros((1, n), dtype=np.int32)
+    cum_d = torch.as_tensor(np.ascontiguousarray(cum, dtype=np.int32), device=X.device)
+    mi_d = torch.as_tensor(m_index, device=X.device)
+    call("fmx_cs_qlabel", ptr(X), ptr(present), ptr(cum_d), ptr(mi_d), ptr(labels), F, D, A, A, n, stream_ptr())
+    return labels
+
+
+def qbucket_mean(labels, R, n_groups: int, prev_row=None, rpresent=None):
+    """Mean return per (factor, date, group) of the groups lagged one row per symbol
+    (fmx_qbucket_mean; composite_factor.py:79-98): labels uint8 [F][D][A] from cs_qlabel,
+    R [D][A] float64 (NaN = no return), prev_row int32 [D][A] (the symbol's previous feature
+    row, -1 = none / not a feature row) or None for the dense grid (row d - 1), rpresent
+    uint8 [D][A] or None.  Returns (mean float64 [F][D][n], count int32 [F][D][n]); the sums
+    are exact, so the result is independent of chunking and of dense-vs-gather addressing."""
+    if (not isinstance(labels, torch.Tensor) or labels.device.type != "cuda" or labels.dtype != torch.uint8
+            or labels.dim() != 3 or not labels.is_contiguous()):
+        raise _lib.FmxError("qbucket_mean: labels must be a contiguous uint8 [F][D][A] device tensor")
+    F, D, A = labels.shape
+    _dense2(R, "R")
+    if tuple(R.shape) != (D, A):
+        raise _lib.FmxError("qbucket_mean: R must be [D][A]")
+    _check_present(rpresent, D, A)
+    if prev_row is not None:
+        prev_row = torch.as_tensor(prev_row, dtype=torch.int32).to(labels.device).contiguous()
+        if tuple(prev_row.shape) != (D, A):
+            raise _lib.FmxError("qbucket_mean: prev_row must be int32 [D][A]")
+    n = int(n_groups)
+    nn = max(n, 0)
+    mean = torch.empty((F, D, nn), dtype=F64, device=labels.device)
+    count = torch.empty((F, D, nn), dtype=torch.int32, device=labels.device)
+    call("fmx_qbucket_mean", ptr(labels), ptr(R), ptr(rpresent), ptr(prev_row), ptr(mean), ptr(count), F, D, A, n,
+         stream_ptr())
+    return mean, count

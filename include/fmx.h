@@ -523,6 +523,37 @@ fmx_status fmx_pnl_daily(const double* W, const double* R, const double* CAP, co
  * the pair-valid (X, R) cells.  out [D][2] = (n, corr); corr NaN for n < 2 or constant. */
 fmx_status fmx_daily_corr(const double* X, const double* R, double* out, int64_t D, int64_t A, void* stream);
 
+/* ---- quantile backtest (composite_factor.py:47-134; csrc/qbacktest.hip) ------------ */
+/* The per-date bucket of every cell (composite_factor.py:71-77: pd.qcut of the date's
+ * rank(method="first") into n_groups bins, group = n_groups - label, 1 = top).  Per
+ * (factor, date) row, m = number of present non-NaN cells; the ordinal rank r in 1..m
+ * breaks ties by the lower asset column; the label is the first k with cum[row][k] >= r.
+ *   cum [M][n_groups] (device int32): row j holds, for one m, the number of ranks 1..m
+ *     whose qcut label is <= k -- filled on the host from pandas' own bin edges;
+ *   m_index [A + 1] (device int32): the row of cum for every m, or -1.
+ * labels [F][D][A] uint8 (dense): 0 = none (absent, NaN, or m <= 1), else the group; a row
+ * whose m has no table row gets 255 on its valid cells (fmx_qbucket_mean then counts none
+ * of them: 255 is outside 1..n_groups).  2 <= n_groups <= 32, A <= 8192. */
+fmx_status fmx_cs_qlabel(const double* X, const uint8_t* present, const int32_t* cum, const int32_t* m_index,
+                         uint8_t* labels, int64_t F, int64_t D, int64_t A, int64_t ld, int32_t n_groups,
+                         void* stream);
+/* The mean return of every (date, group) (composite_factor.py:79-98: the groups shifted one
+ * row per symbol, joined with the returns, group-by mean).  Cell (d, a) of factor f belongs
+ * to group labels[f][prev_row[d][a]][a]; it is kept when that group is in 1..n_groups and
+ * R[d][a] is not NaN (rpresent [D][A], or NULL, marks the returns cells that exist).
+ *   prev_row [D][A] (device int32): the symbol's previous row of the feature index, -1 =
+ *     none or not a feature row; NULL = the dense grid (row d - 1).  The table is read back
+ *     before the launch: an entry outside [-1, D) is FMX_ERR_ARG.
+ * mean [F][D][n_groups] (NaN for an empty group), count [F][D][n_groups] int32.  The sums
+ * are fixed-point integers (exactsum.hpp on returns scaled by 2^48: exact for every term of
+ * magnitude >= 2^-60, smaller terms truncated at 2^-112; the conversion back to double may
+ * round more than once), so the outputs do not depend on the launch geometry, the split of
+ * the factors over workgroups or dense-vs-gather addressing.  Returns of magnitude >= 2^79, or non-finite,
+ * make their group's mean NaN.  2 <= n_groups <= 32, A <= 8192. */
+fmx_status fmx_qbucket_mean(const uint8_t* labels, const double* R, const uint8_t* rpresent, const int32_t* prev_row,
+                            double* mean, int32_t* count, int64_t F, int64_t D, int64_t A, int32_t n_groups,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
     python tools/kbench.py [--dates D --assets A --factors F] [--ops cs_rank,ic,...] [--reps N]
     python tools/kbench.py --ops mvo [--mvo-windows J --factors F --mvo-window W] [--reps N]
     python tools/kbench.py --ops sim_mvo [--dates D --assets A --lookback L --max-weight U] [--reps N]
+    python tools/kbench.py --ops qbacktest [--dates D --assets A --factors F --groups 5,10 --e2e] [--reps N]
 
 The panel is generated on the host with numpy (SURVEY 8(d) statistics: N(0,1), 1% NaN,
 5% rounded to one decimal) for a small factor block and tiled along the factor axis on
@@ -208,8 +209,76 @@ def bench_sim_mvo(D, A, lookback, u, reps):
     print(json.dumps({"sim_mvo": res}))
 
 
+def bench_qbacktest(D, A, F, groups, reps, e2e):
+    """--ops qbacktest: the quantile backtest's two kernels (engine.cs_qlabel, whose cut table
+    and count pass are timed apart from the fmx_cs_qlabel launch, and engine.qbucket_mean on
+    the plain-row and the gather path) and, in the same call and on the same rows,
+    fmx_cs_rank(method="first").  Fractions of the 8 TB/s HBM peak count 9 B per cell for the
+    labels (16 B for the rank) and 1 B per cell plus the returns rows for the means.  --e2e:
+    the public function, pandas in and frames out, device against host."""
+    import time
+    from factormodeling_amd._lib import call, ptr, stream_ptr
+    PEAK = 8e12
+    X, R = panel(D, A, F)
+    cells = float(D) * A * F
+    res = {"dims": [D, A, F], "groups": {}}
+    Y = torch.empty_like(X)
+    ms_rank, _ = _timed(lambda: E.cs_rank(X, "first", out=Y), reps)
+    del Y
+    res["cs_rank_first_ms"] = round(ms_rank, 3)
+    res["cs_rank_first_hbm_frac"] = round(16 * cells / (ms_rank * 1e-3) / PEAK, 4)
+    print(f"cs_rank(first)      {ms_rank:9.3f} ms  {16 * cells / ms_rank / 1e6:8.1f} GB/s", flush=True)
+    prev = torch.as_tensor(np.repeat(np.arange(-1, D - 1, dtype=np.int32)[:, None], A, axis=1), device="cuda")
+    for n in groups:
+        ms_all, lab = _timed(lambda: E.cs_qlabel(X, n), reps)
+        ms = np.unique((~torch.isnan(X)).sum(dim=2).cpu().numpy())
+        ms = [int(m) for m in ms if m >= 2]
+        mi = np.full(A + 1, -1, dtype=np.int32)
+        mi[ms] = np.arange(len(ms), dtype=np.int32)
+        cum = torch.as_tensor(np.stack([E.qcut_cum(m, n) for m in ms]).astype(np.int32), device="cuda")
+        mi = torch.as_tensor(mi, device="cuda")
+        ms_k, _ = _timed(lambda: call("fmx_cs_qlabel", ptr(X), None, ptr(cum), ptr(mi), ptr(lab), F, D, A, A, n,
+                                      stream_ptr()), reps)
+        ms_m, (m0, c0) = _timed(lambda: E.qbucket_mean(lab, R, n), reps)
+        ms_g, (m1, c1) = _timed(lambda: E.qbucket_mean(lab, R, n, prev_row=prev), reps)
+        same = bool(torch.equal(c0, c1)) and m0.cpu().numpy().tobytes() == m1.cpu().numpy().tobytes()
+        mbytes = cells + 8.0 * D * A * -(-F // 16)
+        r = {"qlabel_kernel_ms": round(ms_k, 3), "qlabel_hbm_frac": round(9 * cells / (ms_k * 1e-3) / PEAK, 4),
+             "qlabel_engine_ms": round(ms_all, 3), "distinct_m": len(ms),
+             "vs_cs_rank_first": round(ms_k / ms_rank, 3),
+             "qbucket_mean_ms": round(ms_m, 3), "qbucket_hbm_frac": round(mbytes / (ms_m * 1e-3) / PEAK, 4),
+             "qbucket_gather_ms": round(ms_g, 3), "gather_equals_plain": same}
+        res["groups"][n] = r
+        print(f"n={n}:", r, flush=True)
+        del lab, m0, c0, m1, c1
+    if e2e:
+        import pandas as pd
+        from factormodeling_amd import composite_factor as cf
+        idx = pd.MultiIndex.from_product([pd.bdate_range("2015-01-01", periods=D), [f"S{i:05d}" for i in range(A)]],
+                                         names=["date", "symbol"])
+        df = pd.DataFrame(X.reshape(F, D * A).T.cpu().numpy(), index=idx, columns=[f"f{k}" for k in range(F)])
+        ret = pd.Series(R.reshape(-1).cpu().numpy(), index=idx)
+        n = groups[0]
+        cf.quantile_backtest_log(df.iloc[:, :1], ret, n, backend="device")          # warm-up
+        t = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            dv = cf.quantile_backtest_log(df, ret, n, backend="device")
+            t.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        hs = cf.quantile_backtest_log(df, ret, n, backend="host")
+        th = time.perf_counter() - t0
+        err = max(float(np.nanmax(np.abs(dv[c].to_numpy() - hs[c].to_numpy(dtype=np.float64)))) for c in df.columns)
+        res["e2e"] = {"n_groups": n, "device_s": round(min(t), 4), "host_s": round(th, 3),
+                      "speedup": round(th / min(t), 1), "max_abs_diff": err}
+        print("e2e:", res["e2e"], flush=True)
+    print(json.dumps({"qbacktest": res}))
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--groups", default="5,10")
+    p.add_argument("--e2e", action="store_true")
     p.add_argument("--lookback", type=int, default=60)
     p.add_argument("--max-weight", type=float, default=0.03)
     p.add_argument("--mvo-windows", type=int, default=2400)
@@ -226,6 +295,8 @@ def main():
         return bench_mvo(a.mvo_windows, F, a.mvo_window, a.reps)
     if a.ops == "sim_mvo":        # signal + returns panels only
         return bench_sim_mvo(D, A, a.lookback, a.max_weight, a.reps)
+    if a.ops == "qbacktest":      # its own panel, labels and the cs_rank(first) comparison
+        return bench_qbacktest(D, A, F, [int(g) for g in a.groups.split(",")], a.reps, a.e2e)
     X, R = panel(D, A, F)
     Y = torch.empty_like(X)
     units = float(D) * A * F
