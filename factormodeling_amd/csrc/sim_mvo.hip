@@ -30,96 +30,15 @@
 // The centred Gram is M^-1's source: C C' = sum over active columns, one staged row at a time.
 // All arithmetic is plain fp64 (fma); no fast-math, no cooperative launch, <= 16 waves.
 //
+// The phases (legs, window statistics, Gram, power iteration, sweep, Woodbury apply) are the
+// functions of sim_mvo_common.hpp, shared with sim_mvo_turnover.hip.
+//
 // Caps: A <= 16,384 (SMV_MAX_A), T <= 64 rows per window (SMV_MAX_T).
 #include <vector>
 
-#include "fmx_common.hpp"
+#include "sim_mvo_common.hpp"
 
 namespace fmx {
-
-constexpr int SMV_MAX_A = 16384;
-constexpr int SMV_MAX_T = 64;
-constexpr int SMV_POWER_ITERS = 32;
-constexpr double SMV_RATIO_FLOOR = 1e-3;   // rho >= 0.032 l_max(2 Sigma); DESIGN 14
-constexpr int SMV_RED = 64;                // one reduction buffer: 16 waves x 4 values
-constexpr int SMV_SMALL = 2 * SMV_MAX_T + 2 * SMV_RED + SMV_MAX_T / 2;   // gv, hv, red, rows (in doubles)
-constexpr size_t SMV_LDS_MAX = 160 * 1024;
-
-namespace {
-
-__device__ __forceinline__ double smv_wsum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double smv_wmax(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-
-// Workgroup reduction of (sum a, sum b, f(c), f(d)), f = sum or max, in two halves around a
-// barrier the caller owns.  Two buffers alternate, so the next put needs no barrier of its own.
-template <bool MAXCD>
-__device__ __forceinline__ void smv_put(double* red, int buf, double a, double b, double c, double d) {
-  a = smv_wsum(a);
-  b = smv_wsum(b);
-  c = MAXCD ? smv_wmax(c) : smv_wsum(c);
-  d = MAXCD ? smv_wmax(d) : smv_wsum(d);
-  if ((threadIdx.x & 63) == 0) {
-    double* r = red + buf * SMV_RED + (threadIdx.x >> 6) * 4;
-    r[0] = a;
-    r[1] = b;
-    r[2] = c;
-    r[3] = d;
-  }
-}
-template <bool MAXCD>
-__device__ __forceinline__ void smv_get(const double* red, int buf, double& a, double& b, double& c, double& d) {
-  const int nw = blockDim.x >> 6;
-  const double* r = red + buf * SMV_RED;
-  a = r[0];
-  b = r[1];
-  c = r[2];
-  d = r[3];
-  for (int w = 1; w < nw; ++w) {
-    a += r[4 * w];
-    b += r[4 * w + 1];
-    c = MAXCD ? fmax(c, r[4 * w + 2]) : c + r[4 * w + 2];
-    d = MAXCD ? fmax(d, r[4 * w + 3]) : d + r[4 * w + 3];
-  }
-}
-__device__ __forceinline__ void smv_sum3(double* red, int& buf, double& a, double& b, double& c) {
-  double d = 0.0;
-  smv_put<false>(red, buf, a, b, c, 0.0);
-  __syncthreads();
-  smv_get<false>(red, buf, a, b, c, d);
-  buf ^= 1;
-}
-__device__ __forceinline__ double smv_sum(double* red, int& buf, double a) {
-  double b = 0.0, c = 0.0;
-  smv_sum3(red, buf, a, b, c);
-  return a;
-}
-
-__device__ __forceinline__ bool smv_finite(double v) {
-  return (((uint32_t)__double2hiint(v) >> 20) & 0x7ffu) != 0x7ffu;
-}
-
-// dot of the LDS vector vec [A] with the panel row r [A], by one wave (every lane gets it)
-__device__ __forceinline__ double smv_rowdot(const double* vec, const double* __restrict__ r, int A) {
-  const int lane = threadIdx.x & 63;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  int a = lane;
-  for (; a + 192 < A; a += 256) {
-    a0 = __builtin_fma(vec[a], r[a], a0);
-    a1 = __builtin_fma(vec[a + 64], r[a + 64], a1);
-    a2 = __builtin_fma(vec[a + 128], r[a + 128], a2);
-    a3 = __builtin_fma(vec[a + 192], r[a + 192], a3);
-  }
-  for (; a < A; a += 64) a0 = __builtin_fma(vec[a], r[a], a0);
-  return smv_wsum((a0 + a1) + (a2 + a3));
-}
-
-}  // namespace
 
 // status (info[0]): 0 converged, 1 max_iter reached (last iterate kept), 2 x0 fallback (T = 1,
 // an infeasible leg or a non-finite window), 3 flat day, 4 no returns history (T = 0: the
@@ -140,32 +59,19 @@ __global__ __launch_bounds__(1024) void k_sim_mvo(const double* __restrict__ R0,
   const int64_t j = blockIdx.x;
   double* M = work ? work + j * (SMV_MAX_T * SMV_MAX_T) : sm + A + SMV_SMALL;   // [T * T]
   const int tid = threadIdx.x, NT = blockDim.x;
-  const int lane = tid & 63, wv = tid >> 6, nw = NT >> 6;
   const int T = win_T[j];
   const double* xj = X + j * A;
   const uint8_t* pj = present ? present + j * A : nullptr;
   double* wj = W + j * A;
   double* inf = info + j * 6;
-  int buf = 0;
+  SmvDay d = {R0, A, T, rows, vec, gv, hv, red, M, 0};
+  int& buf = d.buf;
 
   // ---- the day's legs
   int sg[EPT];      // +1 / -1 on the legs, 0 elsewhere
   bool pr[EPT];     // the symbol has a row on this date
-  double cp = 0.0, cn = 0.0, cr = 0.0;
-#pragma unroll
-  for (int e = 0; e < EPT; ++e) {
-    const int a = tid + e * NT;
-    sg[e] = 0;
-    pr[e] = false;
-    if (a < A) {
-      pr[e] = !pj || pj[a];
-      const double xv = xj[a];
-      if (pr[e]) sg[e] = xv > 0.0 ? 1 : (xv < 0.0 ? -1 : 0);
-      cr += pr[e] ? 1.0 : 0.0;
-      cp += sg[e] > 0 ? 1.0 : 0.0;
-      cn += sg[e] < 0 ? 1.0 : 0.0;
-    }
-  }
+  double cp, cn, cr;
+  smv_signs<EPT>(xj, pj, A, sg, pr, cp, cn, cr);
   smv_sum3(red, buf, cp, cn, cr);
   const double npos = cp, nneg = cn, npres = cr;
 
@@ -192,122 +98,22 @@ __global__ __launch_bounds__(1024) void k_sim_mvo(const double* __restrict__ R0,
   if (tid < T) rows[tid] = win_rows[j * Lmax + tid];
   __syncthreads();
   double m[EPT];
-  double dsum = 0.0;
-  {
-    double acc[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) acc[e] = 0.0;
-    for (int k = 0; k < T; ++k) {
-      const double* r = R0 + (int64_t)rows[k] * A;
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) {
-        const int a = tid + e * NT;
-        if (a < A) acc[e] += r[a];
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      m[e] = acc[e] / (double)T;
-      acc[e] = 0.0;
-    }
-    for (int k = 0; k < T; ++k) {
-      const double* r = R0 + (int64_t)rows[k] * A;
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) {
-        const int a = tid + e * NT;
-        if (a < A && pr[e]) {
-          const double c = r[a] - m[e];
-          acc[e] = __builtin_fma(c, c, acc[e]);
-        }
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) dsum += acc[e];
-  }
+  smv_col_means<EPT>(d, m);
+  double dsum = smv_diag_sum<EPT>(d, m, pr);
   dsum = smv_sum(red, buf, dsum);
   const double avg_var = dsum / ((double)(T - 1) * npres) + 1e-6;
   const double q = shrink > 0.0 ? 1.0 - shrink : 1.0;
   const double delta = q * 1e-6 + (shrink > 0.0 ? shrink * avg_var : 0.0);
   const double sc2 = q / (double)(T - 1);
 
-  // ---- centred Gram over the active columns: G_kl = sum_a c_k[a] (X_l[a] - m[a])
-  for (int k = 0; k < T; ++k) {
-    const double* r = R0 + (int64_t)rows[k] * A;
-    double mu = 0.0;
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      const int a = tid + e * NT;
-      if (a < A) {
-        const double c = sg[e] != 0 ? r[a] - m[e] : 0.0;
-        vec[a] = c;
-        mu = __builtin_fma(c, m[e], mu);
-      }
-    }
-    mu = smv_sum(red, buf, mu);   // barrier inside: vec is complete
-    for (int l = wv; l <= k; l += nw) {
-      const double d = smv_rowdot(vec, R0 + (int64_t)rows[l] * A, A) - mu;
-      if (lane == 0) {
-        M[k * T + l] = d;
-        M[l * T + k] = d;
-      }
-    }
-    __syncthreads();
-  }
-
-  // ---- l_max of the Gram: power iteration from a positive start
-  const bool own = tid < T;
-  double lmax = 0.0;
-  {
-    double v = own ? 1.0 + 0.01 * (double)((tid * 37) % 11) : 0.0;
-    for (int it = 0; it < SMV_POWER_ITERS; ++it) {
-      if (own) hv[tid] = v;
-      __syncthreads();
-      double t = 0.0;
-      if (own)
-        for (int r = 0; r < T; ++r) t = __builtin_fma(M[r * T + tid], hv[r], t);
-      double vv = v * v, tt = t * t, z0 = 0.0;
-      smv_sum3(red, buf, vv, tt, z0);
-      lmax = vv > 0.0 ? sqrt(tt / vv) : 0.0;
-      v = tt > 0.0 ? t / sqrt(tt) : 0.0;
-    }
-  }
-  const double l_lo = 2.0 * delta, l_hi = 2.0 * delta + 2.0 * sc2 * lmax;
-  const double ratio = l_lo > SMV_RATIO_FLOOR * l_hi ? l_lo / l_hi : SMV_RATIO_FLOOR;
-  const double rho = l_hi * sqrt(ratio);
+  // ---- centred Gram over the active columns, its l_max, rho
+  smv_gram<EPT>(d, m, sg);
+  const double rho = smv_rho(delta, sc2, smv_lmax(d));
   const double c = 2.0 * delta + rho;
 
-  // ---- M = c/2 I + sc2 G, inverted in place by a symmetric sweep on every pivot (M <- -M^-1)
+  // ---- M = c/2 I + sc2 G, inverted in place
   const int TT = T * T;
-  for (int idx = tid; idx < TT; idx += NT) {
-    const int i = idx / T;
-    M[idx] = sc2 * M[idx] + (idx - i * T == i ? 0.5 * c : 0.0);
-  }
-  __syncthreads();
-  int bad = !(rho > 0.0) || !smv_finite(rho);
-  for (int k = 0; k < T && !bad; ++k) {
-    if (own) hv[tid] = M[k * T + tid];
-    __syncthreads();
-    const double piv = hv[k];
-    if (!(piv > 0.0) || !smv_finite(piv)) {   // uniform: every thread reads the same word
-      bad = 1;
-      break;
-    }
-    const double ip = 1.0 / piv;
-    for (int idx = tid; idx < TT; idx += NT) {
-      const int i = idx / T, cc = idx - i * T;
-      const double ci = hv[i], cj = hv[cc];
-      double nv;
-      if (i == k)
-        nv = (cc == k) ? -ip : cj * ip;
-      else if (cc == k)
-        nv = ci * ip;
-      else
-        nv = __builtin_fma(-ci * ip, cj, M[idx]);
-      M[idx] = nv;
-    }
-    __syncthreads();
-  }
-  if (bad) {   // a non-finite return in the window: the solver has no answer, x0 (:451-459)
+  if (smv_sweep(d, c, sc2, rho)) {   // a non-finite return in the window: the solver has no answer, x0 (:451-459)
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {
       const int a = tid + e * NT;
@@ -326,80 +132,11 @@ __global__ __launch_bounds__(1024) void k_sim_mvo(const double* __restrict__ R0,
   for (int idx = tid; idx < TT; idx += NT) M[idx] = -M[idx];
   __syncthreads();
 
-  // out = K^-1 v on the active columns (v is zero elsewhere); t1 = p1'v, t2 = p2'v
-  double pp[EPT], pn[EPT];
-#pragma unroll
-  for (int e = 0; e < EPT; ++e) pp[e] = pn[e] = 0.0;
-  const double rc = 1.0 / c;
-  auto kapply = [&](const double (&v)[EPT], double (&out)[EPT], double& t1, double& t2) {
-    double mv = 0.0;
-    t1 = 0.0;
-    t2 = 0.0;
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      const int a = tid + e * NT;
-      if (a < A) {
-        vec[a] = v[e];
-        mv = __builtin_fma(m[e], v[e], mv);
-        t1 = __builtin_fma(pp[e], v[e], t1);
-        t2 = __builtin_fma(pn[e], v[e], t2);
-      }
-    }
-    smv_sum3(red, buf, mv, t1, t2);   // barrier inside: vec is complete
-    for (int k = wv; k < T; k += nw) {
-      const double d = smv_rowdot(vec, R0 + (int64_t)rows[k] * A, A);
-      if (lane == 0) gv[k] = d - mv;
-    }
-    __syncthreads();
-    double h = 0.0;
-    if (own) {
-      for (int r = 0; r < T; ++r) h = __builtin_fma(M[r * T + tid], gv[r], h);
-      hv[tid] = h;
-    }
-    const double hs = smv_sum(red, buf, h);   // barrier inside: hv is complete
-    double acc[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) acc[e] = 0.0;
-    for (int k = 0; k < T; ++k) {
-      const double* r = R0 + (int64_t)rows[k] * A;
-      const double hk = hv[k];
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) {
-        const int a = tid + e * NT;
-        if (a < A && sg[e] != 0) acc[e] = __builtin_fma(r[a], hk, acc[e]);
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      const double ct = __builtin_fma(-m[e], hs, acc[e]);
-      out[e] = sg[e] != 0 ? __builtin_fma(-sc2, ct, v[e]) * rc : 0.0;
-    }
-  };
-
   // ---- p+ = K^-1 e+, p- = K^-1 e-, and the 2 x 2 system of the leg multipliers
-  double t1, t2;
-  {
-    double ev[EPT], o1[EPT], o2[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) ev[e] = sg[e] > 0 ? 1.0 : 0.0;
-    kapply(ev, o1, t1, t2);
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) ev[e] = sg[e] < 0 ? 1.0 : 0.0;
-    kapply(ev, o2, t1, t2);
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      pp[e] = o1[e];
-      pn[e] = o2[e];
-    }
-  }
-  double a11 = 0.0, a12 = 0.0, a22 = 0.0;
-#pragma unroll
-  for (int e = 0; e < EPT; ++e) {
-    a11 += sg[e] > 0 ? pp[e] : 0.0;
-    a12 += sg[e] > 0 ? pn[e] : 0.0;
-    a22 += sg[e] < 0 ? pn[e] : 0.0;
-  }
-  smv_sum3(red, buf, a11, a12, a22);
+  double pp[EPT], pn[EPT];
+  const double rc = 1.0 / c;
+  double t1, t2, a11, a12, a22;
+  smv_leg_system<EPT>(d, pp, pn, m, sg, sc2, rc, a11, a12, a22);
   const double rdet = 1.0 / (a11 * a22 - a12 * a12);
 
   // ---- ADMM from x0
@@ -416,7 +153,7 @@ __global__ __launch_bounds__(1024) void k_sim_mvo(const double* __restrict__ R0,
     double b[EPT], kb[EPT];
 #pragma unroll
     for (int e = 0; e < EPT; ++e) b[e] = sg[e] != 0 ? rho * (z[e] - y[e]) : 0.0;
-    kapply(b, kb, t1, t2);
+    smv_kapply<EPT>(d, b, kb, t1, t2, pp, pn, m, sg, sc2, rc);
     const double r1 = t1 - 1.0, r2 = t2 + 1.0;
     const double nup = (r1 * a22 - r2 * a12) * rdet, nun = (a11 * r2 - a12 * r1) * rdet;
     double sp = 0.0, sn = 0.0, ep = 0.0, ed = 0.0;
@@ -466,10 +203,6 @@ __global__ __launch_bounds__(1024) void k_sim_mvo(const double* __restrict__ R0,
     inf[4] = delta;
     inf[5] = rho;
   }
-}
-
-static size_t smv_lds_bytes(int64_t A, int64_t Lmax, bool m_in_lds) {
-  return sizeof(double) * (size_t)(A + SMV_SMALL + (m_in_lds ? Lmax * Lmax : 0));
 }
 
 }  // namespace fmx

@@ -997,6 +997,51 @@ def sim_mvo_books(R0, win_rows, win_T, X, present=None, shrinkage=0.1, max_weigh
     return W, counts, info
 
 
+def sim_mvo_turnover_books(R0, win_rows, win_T, X, present=None, W=None, shrinkage=0.1, max_weight=0.03,
+                           turnover_penalty=0.1, return_weight=0.0, max_iter=20000, eps=1e-9, return_opt=False):
+    """Simulation._daily_trade_list, method 'mvo_turnover' (portfolio_simulation.py:206-248,
+    :463-585) for B independent chains of J dates (fmx_sim_mvo_turnover_books): R0, win_rows and
+    win_T as ``sim_mvo_books``, shared by the chains; X [B][J][A] (or [J][A]: one chain) the
+    signals, present [B][J][A] / [J][A] uint8 or None.  ``W`` [B][J][A] (optional) carries the
+    caller's equal-weight book on the rows of the dates without returns history (win_T = 0):
+    the kernel reads those rows as the next date's previous weights and writes every other row.
+    Returns (W, counts [B][J][2], info [B][J][6]) and, with ``return_opt``, Wopt [B][J][A]: the
+    solver's iterate before the prune / renormalise step."""
+    for t, name, nd in ((R0, "R0", (2,)), (X, "X", (2, 3))):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != F64 or t.dim() not in nd:
+            raise _lib.FmxError(f"sim_mvo_turnover_books: {name} must be a float64 HIP device tensor "
+                                f"({' or '.join(str(n) for n in nd)}-D)")
+    R0, X = R0.contiguous(), as3(X).contiguous()
+    (Dr, A), (B, J, _) = R0.shape, X.shape
+    if X.shape[2] != A or not 1 <= A <= SIM_MVO_MAX_A:
+        raise _lib.FmxError(f"sim_mvo_turnover_books: R0 and X must share 1 <= A <= {SIM_MVO_MAX_A} asset columns")
+    if present is not None:
+        if present.dtype != torch.uint8 or tuple(as3(present).shape) != (B, J, A) or not present.is_contiguous():
+            raise _lib.FmxError("present must be a contiguous uint8 [B][J][A] device tensor")
+    win_rows = torch.as_tensor(win_rows, dtype=torch.int32).to(X.device).contiguous()
+    win_T = torch.as_tensor(win_T, dtype=torch.int32).to(X.device).contiguous()
+    if win_rows.dim() != 2 or win_rows.shape[0] != J or tuple(win_T.shape) != (J,):
+        raise _lib.FmxError("sim_mvo_turnover_books: win_rows must be [J][Lmax] and win_T [J]")
+    Lmax = int(win_rows.shape[1])
+    if not 1 <= Lmax <= SIM_MVO_MAX_T:
+        raise _lib.FmxError(f"sim_mvo_turnover_books: 1 <= Lmax <= {SIM_MVO_MAX_T} window rows supported, got {Lmax}")
+    if W is None:
+        W = torch.zeros((B, J, A), dtype=F64, device=X.device)
+    elif (not isinstance(W, torch.Tensor) or W.device != X.device or W.dtype != F64 or tuple(as3(W).shape) != (B, J, A)
+          or not W.is_contiguous()):
+        raise _lib.FmxError("sim_mvo_turnover_books: W must be a contiguous float64 [B][J][A] tensor on X's device")
+    W = as3(W)
+    Wopt = torch.empty((B, J, A), dtype=F64, device=X.device) if return_opt else None
+    counts = torch.empty((B, J, 2), dtype=F64, device=X.device)
+    info = torch.empty((B, J, 6), dtype=F64, device=X.device)
+    nb = int(_lib.load().fmx_sim_mvo_turnover_books_work_bytes(A, Lmax, J, B))
+    work, wb = _workspace_bytes(X.device, nb)
+    call("fmx_sim_mvo_turnover_books", ptr(R0), int(Dr), int(A), ptr(win_rows), ptr(win_T), Lmax, ptr(X), ptr(present),
+         int(J), int(B), float(shrinkage), float(max_weight), float(turnover_penalty), float(return_weight),
+         int(max_iter), float(eps), ptr(W), ptr(Wopt), ptr(counts), ptr(info), ptr(work), wb, stream_ptr())
+    return (W, counts, info, Wopt) if return_opt else (W, counts, info)
+
+
 def mm_combine(Wf, counts, fw, colmap, wdate):
     """multi_manager combination (multi_manager.py:51-72) of fmx_trade_equal outputs."""
     F, D, A = Wf.shape

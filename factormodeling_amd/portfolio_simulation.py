@@ -17,10 +17,14 @@ the GPU through libfmx:
   (``k_pnl_contrib``);
 * ``_calculate_metrics`` (:799-819): the daily IC (``k_daily_corr``).
 
-'mvo_turnover' (:227-248, :463-746) chains each day's QP to the previous day's solution and
-stays the reference's own host code, as does 'mvo' with ``use_cvxpy=False`` (an explicit
+'mvo_turnover' (:227-248, :463-746) chains each day's QP to the previous day's book.  By
+default it is the reference's own host code; with ``FMX_SIM_MVO_TURNOVER=native`` in the
+environment the chain runs on the device (``k_smt_setup`` / ``k_smt_chain``,
+``simulation.mvo_turnover_trade_list``: every day solved to its optimum, then the reference's
+prune / renormalise step), given ``turnover_penalty`` >= 0 and a finite ``return_weight``.
+Both MVO methods stay host code with ``use_cvxpy=False`` (an explicit
 request for the scipy SLSQP solver), with ``FMX_SIM_MVO=reference`` in the environment,
-without a GPU or outside the kernel's caps: ``_daily_trade_list`` hands these to the
+without a GPU or outside the kernels' caps: ``_daily_trade_list`` hands these to the
 reference's ``Simulation``, loaded by file path from ``FMX_REFERENCE_DIR`` (the user's
 reference checkout; a module of the same name cannot sit on ``sys.path`` next to this
 drop-in), while the P&L and metrics of the resulting weights still run on the device.
@@ -40,7 +44,7 @@ import torch
 from . import _refload
 from . import engine as E
 from .panel import device
-from .simulation import daily_trade_list, mvo_trade_list
+from .simulation import daily_trade_list, mvo_trade_list, mvo_turnover_trade_list
 
 RESULT_COLS = ["log_return", "long_return", "short_return", "long_turnover", "short_turnover", "turnover"]
 
@@ -169,6 +173,8 @@ class Simulation:
         """portfolio_simulation.py:96-154 (equal / linear / mvo on the device)."""
         if self.method == "mvo" and self._mvo_runs_natively():
             return self._native_mvo_trade_list()
+        if self.method == "mvo_turnover" and self._mvo_turnover_runs_natively():
+            return self._native_mvo_turnover_trade_list()
         if self.method in ("mvo", "mvo_turnover"):
             return self._host_trade_list()
         if self.method not in ("equal", "linear"):
@@ -195,6 +201,34 @@ class Simulation:
         if not 1 <= int(self.lookback_period) <= E.SIM_MVO_MAX_T or not self.shrinkage_intensity <= 1.0:
             return False
         return f.index.get_level_values(1).nunique() <= E.SIM_MVO_MAX_A
+
+    def _mvo_turnover_runs_natively(self) -> bool:
+        """'mvo_turnover' stays the reference's host loop unless ``FMX_SIM_MVO_TURNOVER=native``
+        is set; then it runs on the device under the conditions of ``_mvo_runs_natively``, with
+        a ``turnover_penalty`` >= 0 and a finite ``return_weight``."""
+        if os.environ.get("FMX_SIM_MVO_TURNOVER", "").lower() != "native":
+            return False
+        try:
+            tau, r = float(self.turnover_penalty), float(self.return_weight)
+        except (TypeError, ValueError):
+            return False
+        if not (tau >= 0.0 and np.isfinite(tau) and np.isfinite(r)):
+            return False
+        return self._mvo_runs_natively()
+
+    def _native_mvo_turnover_trade_list(self):
+        """portfolio_simulation.py:96-154 with :206-248, :463-585
+        (``simulation.mvo_turnover_trade_list``); unconverged and x0 days are reported once."""
+        shifted, counts, extra = mvo_turnover_trade_list(
+            self.custom_feature, self.returns, self.pct, self.max_weight, int(self.lookback_period),
+            float(self.shrinkage_intensity), float(self.turnover_penalty), float(self.return_weight), return_info=True)
+        info = extra["info"]
+        n1, n2 = int((info[:, 0] == 1).sum()), int((info[:, 0] == 2).sum())
+        if n1 or n2:
+            logging.getLogger("portfolio_simulation").warning(
+                "mvo_turnover: of %d days, %d stopped at the iteration limit (last iterate kept) and %d took the "
+                "equal-leg fallback x0 (one-row window or max_weight too small for a leg)", len(info), n1, n2)
+        return shifted, counts
 
     def _native_mvo_trade_list(self):
         """portfolio_simulation.py:96-154 with :183-204, :315-461 (``simulation.mvo_trade_list``);

@@ -12,8 +12,12 @@ legs + cap-and-redistribute, :172-181, :250-313) and the per-symbol shift (csrc/
 ``lookback_period`` distinct returns dates before it on which one of the day's symbols has a
 row), ``k_sim_mvo`` (csrc/sim_mvo.hip) solves every date's minimum-variance QP in one launch,
 and days without any returns history take the equal-weight book (:188-190).
-``method='mvo_turnover'`` chains each day to the previous day's solution and stays the
-reference's host QP loop.
+
+``mvo_turnover_trade_list(custom_feature, returns, ...)`` is ``method='mvo_turnover'``
+(:206-248, :463-585): the same windows and Sigma, each day's QP with an L1 penalty against
+the previous day's book.  ``k_smt_setup`` prepares every date at once and ``k_smt_chain``
+walks the dates in order on the device (csrc/sim_mvo_turnover.hip); the drop-in
+``Simulation`` routes to it when ``FMX_SIM_MVO_TURNOVER=native`` is set.
 """
 from __future__ import annotations
 
@@ -142,6 +146,54 @@ def _series_out(pi, custom_feature, W, counts):
     return shifted, counts_df
 
 
+def _mvo_inputs(custom_feature, returns, lookback_period, dev):
+    """(pi, R0 [Dr][A] zero-filled returns, win_rows, win_T, X [1][D][A], present) on ``dev``."""
+    pi = panel_index(custom_feature.index)
+    rdates, rd, rs, keep = _returns_grid(pi, returns)
+    r0 = np.zeros((max(len(rdates), 1), pi.A))
+    rv = returns.to_numpy(dtype=np.float64, na_value=np.nan)[keep]
+    r0[rd[keep], rs[keep]] = np.where(np.isnan(rv), 0.0, rv)                                  # fillna(0), :337
+    win_rows, win_T = mvo_window_rows(pi, returns, lookback_period, device=dev)
+    X = torch.as_tensor(pi.to_dense(custom_feature.to_numpy(dtype=np.float64)), device=dev)      # [1][D][A]
+    return pi, torch.as_tensor(r0, device=dev), win_rows, win_T, X, pi.present(dev)
+
+
+def mvo_turnover_trade_list(custom_feature: pd.Series, returns: pd.Series, pct: float = 0.1, max_weight: float = 0.03,
+                            lookback_period: int = 60, shrinkage_intensity: float = 0.1, turnover_penalty: float = 0.1,
+                            return_weight: float = 0.0, return_info: bool = False, max_iter: int = 20000,
+                            eps: float = 1e-9):
+    """``Simulation._daily_trade_list()`` for ``method='mvo_turnover'`` on the device
+    (:206-248, :463-585): the same ``(shifted, counts_df)`` pair as ``mvo_trade_list``.  The
+    dates form one chain: every date's QP carries the L1 penalty ``turnover_penalty`` against
+    the previous date's book and the reward ``return_weight`` on the signal, is solved to its
+    optimum and then pruned / renormalised as the reference does
+    (engine.sim_mvo_turnover_books).  Days without returns history carry the equal-weight book
+    (``k_trade_equal``), which is the next day's previous book like any other.  With
+    ``return_info`` a third value holds ``info`` [D][6], the same-day ``books`` [D][A], the
+    solver's ``opt`` [D][A] before the prune / renormalise step and their ``dates`` / ``symbols``."""
+    custom_feature = by_date(custom_feature)
+    dev = device()
+    pi, R0, win_rows, win_T, X, present = _mvo_inputs(custom_feature, returns, lookback_period, dev)
+    W = torch.zeros_like(X)
+    eq = win_T == 0
+    ce = None
+    if bool(eq.any()):
+        _, ce, we = E.trade_books(X, "equal", pct, max_weight, present=present, nan_absent=False, raw=True)
+        W[0][eq] = we[0][eq]
+    W, counts, info, Wopt = E.sim_mvo_turnover_books(R0, win_rows, win_T, X, present, W, shrinkage_intensity,
+                                                     max_weight, turnover_penalty, return_weight, max_iter, eps,
+                                                     return_opt=True)
+    W, counts, info = W[0], counts[0], info[0]
+    eq = info[:, 0] == 4
+    if bool(eq.any()):
+        counts[eq] = ce[0][eq]
+    shifted, counts_df = _series_out(pi, custom_feature, E.shift_rows(W)[0], counts)
+    if return_info:
+        return shifted, counts_df, {"info": info.cpu().numpy(), "books": W.cpu().numpy(), "opt": Wopt[0].cpu().numpy(),
+                                    "dates": pi.dates, "symbols": pi.symbols}
+    return shifted, counts_df
+
+
 def mvo_trade_list(custom_feature: pd.Series, returns: pd.Series, pct: float = 0.1, max_weight: float = 0.03,
                    lookback_period: int = 60, shrinkage_intensity: float = 0.1, max_iter: int = 20000,
                    eps: float = 1e-9, return_info: bool = False):
@@ -151,17 +203,8 @@ def mvo_trade_list(custom_feature: pd.Series, returns: pd.Series, pct: float = 0
     With ``return_info`` a third value holds the solver's ``info`` [D][6], the same-day
     ``books`` [D][A] (NaN where the feature has no row) and their ``dates`` / ``symbols``."""
     custom_feature = by_date(custom_feature)
-    pi = panel_index(custom_feature.index)
-    dev = device()
-    rdates, rd, rs, keep = _returns_grid(pi, returns)
-    r0 = np.zeros((max(len(rdates), 1), pi.A))
-    rv = returns.to_numpy(dtype=np.float64, na_value=np.nan)[keep]
-    r0[rd[keep], rs[keep]] = np.where(np.isnan(rv), 0.0, rv)                                  # fillna(0), :337
-    win_rows, win_T = mvo_window_rows(pi, returns, lookback_period, device=dev)
-    X = torch.as_tensor(pi.to_dense(custom_feature.to_numpy(dtype=np.float64)), device=dev)      # [1][D][A]
-    present = pi.present(dev)
-    W, counts, info = E.sim_mvo_books(torch.as_tensor(r0, device=dev), win_rows, win_T, X[0], present,
-                                      shrinkage_intensity, max_weight, max_iter, eps)
+    pi, R0, win_rows, win_T, X, present = _mvo_inputs(custom_feature, returns, lookback_period, device())
+    W, counts, info = E.sim_mvo_books(R0, win_rows, win_T, X[0], present, shrinkage_intensity, max_weight, max_iter, eps)
     eq = info[:, 0] == 4
     if bool(eq.any()):
         _, ce, we = E.trade_books(X, "equal", pct, max_weight, present=present, nan_absent=False, raw=True)

@@ -509,6 +509,36 @@ fmx_status fmx_sim_mvo_books(const double* R0, int64_t Dr, int64_t A, const int3
                              int64_t Lmax, const double* X, const uint8_t* present, int64_t J, double shrinkage,
                              double max_weight, int32_t max_iter, double eps, double* W, double* counts,
                              double* info, void* work, int64_t work_bytes, void* stream);
+/* Method 'mvo_turnover' (portfolio_simulation.py:96-154, :206-248, :463-585): B independent
+ * chains of J dates over one returns panel (csrc/sim_mvo_turnover.hip).  Per date, with Sigma,
+ * the legs, the exits and the status codes of fmx_sim_mvo_books,
+ *   min w'Sigma w + tau sum_i |w_i - p_i| - r sum_i x_i w_i   under the same constraints,
+ * tau = turnover_penalty >= 0, r = return_weight (finite; either is FMX_ERR_ARG otherwise).
+ * p is the chain's last book, whatever kind of day produced it, aligned to today's rows: 0
+ * where the symbol had no row on the previous date, all zeros on the first date.  A set-up
+ * kernel prepares what does not depend on p for all B * J dates at once; a second kernel,
+ * one workgroup per chain, solves the dates in order (ADMM with a soft-threshold z-step and
+ * the dual started at +-tau / rho), then applies the reference's post-solve step (:553-573)
+ * on solved days: |w| < 1e-6 -> 0 per leg and, when both leg sums stay > 0, each leg divided
+ * by its (exactly rounded) sum.  No host synchronisation between dates.
+ *   R0, win_rows, win_T, Lmax: as fmx_sim_mvo_books, shared by the chains;
+ *   X [B][J][A], present [B][J][A] or NULL;
+ *   W [B][J][A] in/out: the row of a status-4 date (win_T = 0 and both legs present) arrives
+ *     holding the caller's equal-weight book and is read as the next date's p; every other row
+ *     is written (0 on present cells outside the legs, NaN on absent cells);
+ *   Wopt [B][J][A] or NULL: the solver's z before the post-solve step -- exactly p_i on cells
+ *     that did not move, exactly 0 or +-min(u, 1) at the box ends; the book itself on days
+ *     without a solve;
+ *   counts [B][J][2] (0, 0 on status 3 and 4), info [B][J][6] as fmx_sim_mvo_books, the dual
+ *     residual relative to |2 Sigma x - r x_sig|_inf.
+ * work: fmx_sim_mvo_turnover_books_work_bytes(A, Lmax, J, B) bytes, always needed. */
+int64_t fmx_sim_mvo_turnover_books_work_bytes(int64_t A, int64_t Lmax, int64_t J, int64_t B);
+fmx_status fmx_sim_mvo_turnover_books(const double* R0, int64_t Dr, int64_t A, const int32_t* win_rows,
+                                      const int32_t* win_T, int64_t Lmax, const double* X, const uint8_t* present,
+                                      int64_t J, int64_t B, double shrinkage, double max_weight,
+                                      double turnover_penalty, double return_weight, int32_t max_iter, double eps,
+                                      double* W, double* Wopt, double* counts, double* info, void* work,
+                                      int64_t work_bytes, void* stream);
 
 /* ---- portfolio P&L (portfolio_simulation.py:748-819) ---------- */
 /* Replaces Simulation._daily_portfolio_returns' per-date sums on the aligned [D][A] grid

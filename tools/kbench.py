@@ -3,6 +3,8 @@
     python tools/kbench.py [--dates D --assets A --factors F] [--ops cs_rank,ic,...] [--reps N]
     python tools/kbench.py --ops mvo [--mvo-windows J --factors F --mvo-window W] [--reps N]
     python tools/kbench.py --ops sim_mvo [--dates D --assets A --lookback L --max-weight U] [--reps N]
+    python tools/kbench.py --ops sim_mvo_turnover [--dates D --assets A --lookback L --max-weight U --penalty T
+                                                  --return-weight R --chains B] [--reps N]
     python tools/kbench.py --ops qbacktest [--dates D --assets A --factors F --groups 5,10 --e2e] [--reps N]
 
 The panel is generated on the host with numpy (SURVEY 8(d) statistics: N(0,1), 1% NaN,
@@ -209,6 +211,40 @@ def bench_sim_mvo(D, A, lookback, u, reps):
     print(json.dumps({"sim_mvo": res}))
 
 
+def bench_sim_mvo_turnover(D, A, lookback, u, tau, rw, B, reps):
+    """--ops sim_mvo_turnover: the chained mvo_turnover trade list
+    (engine.sim_mvo_turnover_books) for B independent chains of D dates over one returns panel.
+    Each chain's signal keeps its sign from one day to the next on all but a tenth of the cells
+    (a fresh draw there).  Reports ms per call (set-up and chain kernels together), ADMM
+    iterations mean / max and the histogram of statuses."""
+    rng = np.random.default_rng(0)
+    R = 0.01 * (0.6 * rng.standard_normal((D, 1)) + rng.standard_normal((D, A)) * rng.uniform(0.3, 2.0, A))
+    X = np.empty((B, D, A))
+    X[:, 0] = rng.standard_normal((B, A))
+    for j in range(1, D):
+        redraw = rng.random((B, A)) < 0.1
+        X[:, j] = np.where(redraw, rng.standard_normal((B, A)), X[:, j - 1])
+    X[rng.random((B, 1, A)).repeat(D, axis=1) < 0.05] = 0.0
+    T = np.minimum(np.arange(D), lookback).astype(np.int32)
+    L = min(lookback, max(D - 1, 1))
+    rows = np.zeros((D, L), dtype=np.int32)
+    for j in range(D):
+        rows[j, :T[j]] = np.arange(j - T[j], j)
+    R0, Xd = torch.as_tensor(R, device="cuda"), torch.as_tensor(X, device="cuda")
+    rows_d, T_d = torch.as_tensor(rows, device="cuda"), torch.as_tensor(T, device="cuda")
+    W0 = torch.zeros_like(Xd)
+    W0[:, 0] = E.trade_books(Xd[:, :1].contiguous(), "equal", 0.1, u, nan_absent=False, raw=True)[2][:, 0]
+    ms, (W, counts, info) = _timed(lambda: E.sim_mvo_turnover_books(R0, rows_d, T_d, Xd, None, W0, 0.1, u, tau, rw), reps)
+    info = info.cpu().numpy().reshape(-1, 6)
+    it = info[info[:, 0] <= 1, 1]
+    res = {"D": D, "A": A, "lookback": lookback, "max_weight": u, "penalty": tau, "return_weight": rw, "chains": B,
+           "ms": round(ms, 3), "ms_per_chain_date": round(ms / max(len(it), 1) * B, 4),
+           "status_counts": {int(k): int((info[:, 0] == k).sum()) for k in np.unique(info[:, 0])},
+           "iter_mean": round(float(it.mean()), 1), "iter_max": int(it.max()),
+           "work_MiB": round(_lib.load().fmx_sim_mvo_turnover_books_work_bytes(A, L, D, B) / 2 ** 20, 1)}
+    print(json.dumps({"sim_mvo_turnover": res}))
+
+
 def bench_qbacktest(D, A, F, groups, reps, e2e):
     """--ops qbacktest: the quantile backtest's two kernels (engine.cs_qlabel, whose cut table
     and count pass are timed apart from the fmx_cs_qlabel launch, and engine.qbucket_mean on
@@ -281,6 +317,9 @@ def main():
     p.add_argument("--e2e", action="store_true")
     p.add_argument("--lookback", type=int, default=60)
     p.add_argument("--max-weight", type=float, default=0.03)
+    p.add_argument("--penalty", type=float, default=0.1)
+    p.add_argument("--return-weight", type=float, default=0.0)
+    p.add_argument("--chains", type=int, default=1)
     p.add_argument("--mvo-windows", type=int, default=2400)
     p.add_argument("--mvo-window", type=int, default=120)
     p.add_argument("--dates", type=int, default=2520)
@@ -295,6 +334,8 @@ def main():
         return bench_mvo(a.mvo_windows, F, a.mvo_window, a.reps)
     if a.ops == "sim_mvo":        # signal + returns panels only
         return bench_sim_mvo(D, A, a.lookback, a.max_weight, a.reps)
+    if a.ops == "sim_mvo_turnover":
+        return bench_sim_mvo_turnover(D, A, a.lookback, a.max_weight, a.penalty, a.return_weight, a.chains, a.reps)
     if a.ops == "qbacktest":      # its own panel, labels and the cs_rank(first) comparison
         return bench_qbacktest(D, A, F, [int(g) for g in a.groups.split(",")], a.reps, a.e2e)
     X, R = panel(D, A, F)
