@@ -103,6 +103,11 @@ SIGNATURES = {
     "fmx_sim_mvo_turnover_books": [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_dbl, c_dbl, c_dbl,
                                    c_dbl, c_i32, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "fmx_sim_mvo_turnover_books_work_bytes": [c_i64, c_i64, c_i64, c_i64],
+    "fmx_sim_mvo_turnover_chains": [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_dbl, c_dbl,
+                                    c_dbl, c_dbl, c_i32, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "fmx_sim_mvo_turnover_chains_work_bytes": [c_i64, c_i64, c_i64, c_i64],
+    "fmx_sim_mvo_window_rows": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "fmx_sim_mvo_window_rows_work_bytes": [c_i64, c_i64, c_i64],
     "fmx_mm_combine": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp],
     "fmx_pnl_daily": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp],
     "fmx_daily_corr": [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp],
@@ -116,7 +121,8 @@ _RESTYPES = {"fmx_last_error": c_cp, "fmx_build_variant": c_cp, "fmx_ic_ranked_w
              "fmx_gram_fused_work_bytes": c_i64, "fmx_corr_prune_windows_work_bytes": c_i64,
              "fmx_cs_rank_sorted_work_bytes": c_i64, "fmx_group_rank_sorted_work_bytes": c_i64, "fmx_gram_exact_work_bytes": c_i64,
              "fmx_mvo_windows_work_bytes": c_i64, "fmx_sim_mvo_books_work_bytes": c_i64,
-             "fmx_sim_mvo_turnover_books_work_bytes": c_i64,
+             "fmx_sim_mvo_turnover_books_work_bytes": c_i64, "fmx_sim_mvo_turnover_chains_work_bytes": c_i64,
+             "fmx_sim_mvo_window_rows_work_bytes": c_i64,
              "fmx_debug_exact_fold": None}
 
 # constants mirrored from include/fmx.h

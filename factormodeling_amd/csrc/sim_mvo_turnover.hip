@@ -36,6 +36,12 @@
 //                not depend on the reduction order.  The book stays in registers as the next p:
 //                the same thread owns a column on every date.
 //
+// fmx_sim_mvo_turnover_chains (multi_manager's managers): every chain may have its own
+// window tables (row b * wchain + j; wchain = 0 is the shared table of fmx_sim_mvo_turnover_books)
+// and, with skip_absent, its own date list: a (chain, date) without a present cell gets status 5
+// from the set-up, and the chain writes a NaN row and NaN counts and leaves its book untouched, so
+// the next date's p is the book of the chain's last date with rows (:100, :206-225).
+//
 // Wopt (optional) is z before the post-solve step: exactly p_i on cells that did not move and
 // exactly 0 / +-u at the box ends.  u is used as min(u, 1): with a leg that sums to 1 the two
 // boxes hold the same books.
@@ -95,7 +101,8 @@ __global__ __launch_bounds__(1024) void k_smt_setup(const double* __restrict__ R
                                                     const int32_t* __restrict__ win_rows, int Lmax,
                                                     const int32_t* __restrict__ win_T, const double* __restrict__ X,
                                                     const uint8_t* __restrict__ present, int J, double shrink, double u,
-                                                    double* __restrict__ work, int64_t stride) {
+                                                    double* __restrict__ work, int64_t stride, int64_t wchain,
+                                                    int skip_absent) {
   extern __shared__ double sm[];
   double* vec = sm;                          // [A]
   double* gv = vec + A;                      // [SMV_MAX_T]
@@ -103,9 +110,9 @@ __global__ __launch_bounds__(1024) void k_smt_setup(const double* __restrict__ R
   double* red = hv + SMV_MAX_T;              // [2 * SMV_RED]
   int* rows = (int*)(red + 2 * SMV_RED);     // [SMV_MAX_T]
   const int64_t bj = blockIdx.x;
-  const int64_t j = bj % J;
+  const int64_t wj = (bj / J) * wchain + bj % J;   // the date's row of the window tables (wchain 0: shared)
   const int tid = threadIdx.x;
-  const int T = win_T[j];
+  const int T = win_T[wj];
   double* slot = work + bj * stride;
   SmvDay d = {R0, A, T, rows, vec, gv, hv, red, slot + SMT_HDR, 0};
 
@@ -118,10 +125,12 @@ __global__ __launch_bounds__(1024) void k_smt_setup(const double* __restrict__ R
   const bool flat = npos == 0.0 || nneg == 0.0 || npres < 2.0;
   const bool feasible = u * npos >= 1.0 - 1e-12 && u * nneg >= 1.0 - 1e-12;
   double status = -1.0, delta = 0.0, sc2 = 0.0, rho = 0.0;
-  if (flat || T <= 1 || !feasible) {
+  if (skip_absent && npres == 0.0) {
+    status = 5.0;   // no row at all: not a date of this chain
+  } else if (flat || T <= 1 || !feasible) {
     status = flat ? 3.0 : (T == 0 ? 4.0 : 2.0);
   } else {
-    if (tid < T) rows[tid] = win_rows[j * Lmax + tid];
+    if (tid < T) rows[tid] = win_rows[wj * Lmax + tid];
     __syncthreads();
     double m[EPT];
     smv_col_means<EPT>(d, m);
@@ -156,7 +165,8 @@ __global__ __launch_bounds__(1024) void k_smt_chain(const double* __restrict__ R
                                                     const uint8_t* __restrict__ present, int J, double u, double tau,
                                                     double rw, int max_iter, double eps, double* W, double* Wopt,
                                                     double* __restrict__ counts, double* __restrict__ info,
-                                                    const double* work, int64_t stride, int m_in_lds) {
+                                                    const double* work, int64_t stride, int m_in_lds,
+                                                    int64_t wchain) {
   extern __shared__ double sm[];
   double* vec = sm;                          // [A]
   double* gv = vec + A;                      // [SMV_MAX_T]
@@ -184,7 +194,25 @@ __global__ __launch_bounds__(1024) void k_smt_chain(const double* __restrict__ R
     __syncthreads();   // the previous date is done with rows, M and the vectors
     const int st0 = (int)slot[0];
     const double npos = slot[1], nneg = slot[2], delta = slot[3], sc2 = slot[4], rho = slot[5];
-    const int T = win_T[j];
+    const int64_t wr = b * wchain + j;
+    const int T = win_T[wr];
+
+    if (st0 == 5) {   // skip_absent: every cell is absent; the book in registers is not touched
+#pragma unroll
+      for (int e = 0; e < EPT; ++e) {
+        const int a = tid + e * NT;
+        if (a < A) {
+          wj[a] = qnan();
+          if (oj) oj[a] = qnan();
+        }
+      }
+      if (tid == 0) {
+        counts[2 * bj] = counts[2 * bj + 1] = qnan();
+        inf[0] = 5.0;
+        inf[1] = inf[2] = inf[3] = inf[4] = inf[5] = 0.0;
+      }
+      continue;
+    }
 
     int sg[EPT];
     bool pr[EPT];
@@ -222,7 +250,7 @@ __global__ __launch_bounds__(1024) void k_smt_chain(const double* __restrict__ R
     }
 
     // ---- the window, M^-1 from the set-up, p+-, the 2 x 2 system
-    if (tid < T) rows[tid] = win_rows[j * Lmax + tid];
+    if (tid < T) rows[tid] = win_rows[wr * Lmax + tid];
     const double* Ms = slot + SMT_HDR;
     if (m_in_lds)
       for (int idx = tid; idx < T * T; idx += NT) Mlds[idx] = Ms[idx];
@@ -376,12 +404,17 @@ extern "C" int64_t fmx_sim_mvo_turnover_books_work_bytes(int64_t A, int64_t Lmax
   return (int64_t)sizeof(double) * B * J * (SMT_HDR + Lmax * Lmax);
 }
 
-extern "C" fmx_status fmx_sim_mvo_turnover_books(const double* R0, int64_t Dr, int64_t A, const int32_t* win_rows,
-                                                 const int32_t* win_T, int64_t Lmax, const double* X,
-                                                 const uint8_t* present, int64_t J, int64_t B, double shrinkage,
-                                                 double max_weight, double turnover_penalty, double return_weight,
-                                                 int32_t max_iter, double eps, double* W, double* Wopt, double* counts,
-                                                 double* info, void* work, int64_t work_bytes, void* stream) {
+extern "C" int64_t fmx_sim_mvo_turnover_chains_work_bytes(int64_t A, int64_t Lmax, int64_t J, int64_t B) {
+  return fmx_sim_mvo_turnover_books_work_bytes(A, Lmax, J, B);
+}
+
+// Both entry points: win_stride is the number of table rows between two chains' window tables
+// (0: one table shared by the chains, J: one per chain).
+static fmx_status smt_run(const double* R0, int64_t Dr, int64_t A, const int32_t* win_rows, const int32_t* win_T,
+                          int64_t Lmax, int64_t win_stride, const double* X, const uint8_t* present, int64_t J,
+                          int64_t B, double shrinkage, double max_weight, double turnover_penalty, double return_weight,
+                          int32_t max_iter, double eps, int32_t skip_absent, double* W, double* Wopt, double* counts,
+                          double* info, void* work, int64_t work_bytes, void* stream) {
   FMX_ARG(Dr >= 0 && J >= 0 && B >= 0 && B <= 0x7fffffff && J * B <= 0x7fffffff, "sim_mvo_turnover: bad dims");
   FMX_ARG(A >= 1 && A <= SMV_MAX_A, "sim_mvo_turnover: 1 <= A <= 16384");
   FMX_ARG(Lmax >= 1 && Lmax <= SMV_MAX_T, "sim_mvo_turnover: 1 <= Lmax <= 64 window rows");
@@ -392,15 +425,17 @@ extern "C" fmx_status fmx_sim_mvo_turnover_books(const double* R0, int64_t Dr, i
   FMX_ARG(turnover_penalty >= 0.0 && std::isfinite(turnover_penalty), "sim_mvo_turnover: turnover_penalty must be finite and >= 0");
   FMX_ARG(std::isfinite(return_weight), "sim_mvo_turnover: return_weight must be finite");
   FMX_ARG(max_iter >= 1 && eps > 0.0, "sim_mvo_turnover: max_iter >= 1 and eps > 0");
+  FMX_ARG(win_stride == 0 || win_stride == J, "sim_mvo_turnover: the window tables' chain stride must be 0 or J");
   if (J == 0 || B == 0) return FMX_OK;
   hipStream_t s = as_stream(stream);
   // the row lists are read back and checked: an index outside the panel is an argument error
+  const int64_t NR = win_stride == 0 ? J : B * J;   // rows of the window tables
   {
-    std::vector<int32_t> ht((size_t)J), hr((size_t)(J * Lmax));
+    std::vector<int32_t> ht((size_t)NR), hr((size_t)(NR * Lmax));
     FMX_HIP(hipMemcpyAsync(ht.data(), win_T, sizeof(int32_t) * ht.size(), hipMemcpyDeviceToHost, s));
     FMX_HIP(hipMemcpyAsync(hr.data(), win_rows, sizeof(int32_t) * hr.size(), hipMemcpyDeviceToHost, s));
     FMX_HIP(hipStreamSynchronize(s));
-    for (int64_t j = 0; j < J; ++j) {
+    for (int64_t j = 0; j < NR; ++j) {
       FMX_ARG(ht[j] >= 0 && ht[j] <= Lmax, "sim_mvo_turnover: win_T outside [0, Lmax]");
       for (int32_t k = 0; k < ht[j]; ++k)
         FMX_ARG(hr[j * Lmax + k] >= 0 && hr[j * Lmax + k] < Dr,
@@ -426,13 +461,37 @@ extern "C" fmx_status fmx_sim_mvo_turnover_books(const double* R0, int64_t Dr, i
   if (lds_chain > 64 * 1024)
     FMX_HIP(hipFuncSetAttribute(fc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_chain));
   int Ai = (int)A, Li = (int)Lmax, Ji = (int)J, mi = max_iter, ml = m_in_lds;
-  int64_t st = stride;
+  int64_t st = stride, wc = win_stride;
+  int sk = skip_absent ? 1 : 0;
   void* a1[] = {(void*)&R0, (void*)&Ai, (void*)&win_rows, (void*)&Li, (void*)&win_T, (void*)&X, (void*)&present,
-                (void*)&Ji, (void*)&shrinkage, (void*)&max_weight, (void*)&wk, (void*)&st};
+                (void*)&Ji, (void*)&shrinkage, (void*)&max_weight, (void*)&wk, (void*)&st, (void*)&wc, (void*)&sk};
   FMX_HIP(hipLaunchKernel(fs, dim3((unsigned)(B * J)), dim3(nt), a1, lds_setup, s));
   void* a2[] = {(void*)&R0, (void*)&Ai, (void*)&win_rows, (void*)&Li, (void*)&win_T, (void*)&X, (void*)&present,
                 (void*)&Ji, (void*)&max_weight, (void*)&turnover_penalty, (void*)&return_weight, (void*)&mi,
-                (void*)&eps, (void*)&W, (void*)&Wopt, (void*)&counts, (void*)&info, (void*)&wk, (void*)&st, (void*)&ml};
+                (void*)&eps, (void*)&W, (void*)&Wopt, (void*)&counts, (void*)&info, (void*)&wk, (void*)&st, (void*)&ml,
+                (void*)&wc};
   FMX_HIP(hipLaunchKernel(fc, dim3((unsigned)B), dim3(nt), a2, lds_chain, s));
   return FMX_OK;
+}
+
+extern "C" fmx_status fmx_sim_mvo_turnover_books(const double* R0, int64_t Dr, int64_t A, const int32_t* win_rows,
+                                                 const int32_t* win_T, int64_t Lmax, const double* X,
+                                                 const uint8_t* present, int64_t J, int64_t B, double shrinkage,
+                                                 double max_weight, double turnover_penalty, double return_weight,
+                                                 int32_t max_iter, double eps, double* W, double* Wopt, double* counts,
+                                                 double* info, void* work, int64_t work_bytes, void* stream) {
+  return smt_run(R0, Dr, A, win_rows, win_T, Lmax, 0, X, present, J, B, shrinkage, max_weight, turnover_penalty,
+                 return_weight, max_iter, eps, 0, W, Wopt, counts, info, work, work_bytes, stream);
+}
+
+extern "C" fmx_status fmx_sim_mvo_turnover_chains(const double* R0, int64_t Dr, int64_t A, const int32_t* win_rows,
+                                                  const int32_t* win_T, int64_t Lmax, int64_t win_stride,
+                                                  const double* X, const uint8_t* present, int64_t J, int64_t B,
+                                                  double shrinkage, double max_weight, double turnover_penalty,
+                                                  double return_weight, int32_t max_iter, double eps,
+                                                  int32_t skip_absent, double* W, double* Wopt, double* counts,
+                                                  double* info, void* work, int64_t work_bytes, void* stream) {
+  return smt_run(R0, Dr, A, win_rows, win_T, Lmax, win_stride, X, present, J, B, shrinkage, max_weight,
+                 turnover_penalty, return_weight, max_iter, eps, skip_absent, W, Wopt, counts, info, work, work_bytes,
+                 stream);
 }

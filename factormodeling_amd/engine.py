@@ -1042,6 +1042,85 @@ def sim_mvo_turnover_books(R0, win_rows, win_T, X, present=None, W=None, shrinka
     return (W, counts, info, Wopt) if return_opt else (W, counts, info)
 
 
+def sim_mvo_turnover_chains(R0, win_rows, win_T, X, present=None, W=None, shrinkage=0.1, max_weight=0.03,
+                            turnover_penalty=0.1, return_weight=0.0, max_iter=20000, eps=1e-9, skip_absent=True,
+                            return_opt=False):
+    """``sim_mvo_turnover_books`` for B chains with their own windows and their own date lists
+    (fmx_sim_mvo_turnover_chains): win_rows [B][J][Lmax] / win_T [B][J] hold every chain's
+    tables ([J][Lmax] / [J]: one table shared by the chains).  With ``skip_absent`` a (chain,
+    date) without a present cell is not a date of that chain: NaN row, NaN counts, info[0] = 5,
+    and the chain's previous book stays the one of its last date with rows.  Returns
+    (W [B][J][A], counts [B][J][2], info [B][J][6]) and Wopt with ``return_opt``."""
+    for t, name, nd in ((R0, "R0", (2,)), (X, "X", (2, 3))):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != F64 or t.dim() not in nd:
+            raise _lib.FmxError(f"sim_mvo_turnover_chains: {name} must be a float64 HIP device tensor "
+                                f"({' or '.join(str(n) for n in nd)}-D)")
+    R0, X = R0.contiguous(), as3(X).contiguous()
+    (Dr, A), (B, J, _) = R0.shape, X.shape
+    if X.shape[2] != A or not 1 <= A <= SIM_MVO_MAX_A:
+        raise _lib.FmxError(f"sim_mvo_turnover_chains: R0 and X must share 1 <= A <= {SIM_MVO_MAX_A} asset columns")
+    if present is not None:
+        if present.dtype != torch.uint8 or tuple(as3(present).shape) != (B, J, A) or not present.is_contiguous():
+            raise _lib.FmxError("present must be a contiguous uint8 [B][J][A] device tensor")
+    win_rows = torch.as_tensor(win_rows, dtype=torch.int32).to(X.device).contiguous()
+    win_T = torch.as_tensor(win_T, dtype=torch.int32).to(X.device).contiguous()
+    shared = win_T.dim() == 1
+    if shared:
+        ok = win_rows.dim() == 2 and win_rows.shape[0] == J and tuple(win_T.shape) == (J,)
+    else:
+        ok = win_rows.dim() == 3 and tuple(win_rows.shape[:2]) == (B, J) and tuple(win_T.shape) == (B, J)
+    if not ok:
+        raise _lib.FmxError("sim_mvo_turnover_chains: win_rows must be [B][J][Lmax] and win_T [B][J] "
+                            "(or [J][Lmax] and [J], shared by the chains)")
+    Lmax = int(win_rows.shape[-1])
+    if not 1 <= Lmax <= SIM_MVO_MAX_T:
+        raise _lib.FmxError(f"sim_mvo_turnover_chains: 1 <= Lmax <= {SIM_MVO_MAX_T} window rows supported, got {Lmax}")
+    if W is None:
+        W = torch.zeros((B, J, A), dtype=F64, device=X.device)
+    elif (not isinstance(W, torch.Tensor) or W.device != X.device or W.dtype != F64 or tuple(as3(W).shape) != (B, J, A)
+          or not W.is_contiguous()):
+        raise _lib.FmxError("sim_mvo_turnover_chains: W must be a contiguous float64 [B][J][A] tensor on X's device")
+    W = as3(W)
+    Wopt = torch.empty((B, J, A), dtype=F64, device=X.device) if return_opt else None
+    counts = torch.empty((B, J, 2), dtype=F64, device=X.device)
+    info = torch.empty((B, J, 6), dtype=F64, device=X.device)
+    nb = int(_lib.load().fmx_sim_mvo_turnover_chains_work_bytes(A, Lmax, J, B))
+    work, wb = _workspace_bytes(X.device, nb)
+    call("fmx_sim_mvo_turnover_chains", ptr(R0), int(Dr), int(A), ptr(win_rows), ptr(win_T), Lmax, 0 if shared else int(J),
+         ptr(X), ptr(present), int(J), int(B), float(shrinkage), float(max_weight), float(turnover_penalty),
+         float(return_weight), int(max_iter), float(eps), int(bool(skip_absent)), ptr(W), ptr(Wopt), ptr(counts),
+         ptr(info), ptr(work), wb, stream_ptr())
+    return (W, counts, info, Wopt) if return_opt else (W, counts, info)
+
+
+def sim_mvo_window_rows(fpresent, rpresent, nbefore, lookback: int):
+    """The returns windows of N (manager, date) rows in one pass (fmx_sim_mvo_window_rows;
+    the rule of ``simulation.mvo_window_rows``): fpresent [N][A] uint8 the rows' present
+    symbols, rpresent [Dr][A] uint8 the returns' rows, nbefore [N] int32 the number of returns
+    dates before each row's date.  Returns (win_rows int32 [N][Lmax] ascending, unused tail 0;
+    win_T int32 [N]) with Lmax = min(lookback, Dr), at least 1."""
+    for t, name in ((fpresent, "fpresent"), (rpresent, "rpresent")):
+        if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.uint8 or t.dim() != 2
+                or not t.is_contiguous()):
+            raise _lib.FmxError(f"sim_mvo_window_rows: {name} must be a contiguous uint8 2-D HIP device tensor")
+    (N, A), Dr = fpresent.shape, rpresent.shape[0]
+    if rpresent.shape[1] != A or not 1 <= A <= SIM_MVO_MAX_A:
+        raise _lib.FmxError(f"sim_mvo_window_rows: the masks must share 1 <= A <= {SIM_MVO_MAX_A} asset columns")
+    if not 1 <= int(lookback) <= SIM_MVO_MAX_T:
+        raise _lib.FmxError(f"sim_mvo_window_rows: 1 <= lookback <= {SIM_MVO_MAX_T} supported, got {lookback}")
+    nbefore = torch.as_tensor(nbefore, dtype=torch.int32).to(fpresent.device).contiguous()
+    if tuple(nbefore.shape) != (N,):
+        raise _lib.FmxError("sim_mvo_window_rows: nbefore must be [N]")
+    Lmax = max(1, min(int(lookback), Dr))
+    win_rows = torch.empty((N, Lmax), dtype=torch.int32, device=fpresent.device)
+    win_T = torch.empty((N,), dtype=torch.int32, device=fpresent.device)
+    nb = int(_lib.load().fmx_sim_mvo_window_rows_work_bytes(N, A, Dr))
+    work, wb = _workspace_bytes(fpresent.device, nb)
+    call("fmx_sim_mvo_window_rows", ptr(fpresent), ptr(rpresent), ptr(nbefore), int(N), int(A), int(Dr), Lmax,
+         ptr(win_rows), ptr(win_T), ptr(work), wb, stream_ptr())
+    return win_rows, win_T
+
+
 def mm_combine(Wf, counts, fw, colmap, wdate):
     """multi_manager combination (multi_manager.py:51-72) of fmx_trade_equal outputs."""
     F, D, A = Wf.shape

@@ -6,10 +6,15 @@ Simulation._daily_trade_list over ``factors_df[fac].dropna()`` with the settings
 NaN cells = no row), and each weight date folds the managers' books and counts in
 ``factor_weights`` column order (``k_mm_combine``).  Returns the reference's
 ``(final_weights, final_counts)``: nonzero weights over ``(date, symbol)``, counts indexed
-by date.  'mvo' / 'mvo_turnover' managers (a QP per date) take their books from
-``compute_manager_weights`` -- the drop-in ``Simulation._daily_trade_list``, which solves
-'mvo' on the device one manager at a time and hands 'mvo_turnover' (and 'mvo' with
-``use_cvxpy=False``) to the reference's own solvers -- and fold on the device like the others.  Columns
+by date.  'mvo' / 'mvo_turnover' managers (a QP per date) are solved for all managers in one
+device pass as well (``simulation.mvo_manager_books``: one returns upload, a window per
+(manager, date), 'mvo' as one launch over all (manager, date) rows, 'mvo_turnover' as one
+chain per manager over the manager's own dates) whenever the method runs natively
+(``simulation.mvo_runs_natively``; 'mvo_turnover' needs ``FMX_SIM_MVO_TURNOVER=native`` on top,
+``simulation.mvo_turnover_runs_natively``).  Otherwise -- ``use_cvxpy=False``,
+``FMX_SIM_MVO=reference``, no GPU, inputs outside the kernels' caps -- their books come from
+``compute_manager_weights``, the drop-in ``Simulation._daily_trade_list``, one manager at a
+time (``_host_books``), and fold on the device like the others.  Columns
 absent from ``factors_df`` log the reference's warning (:42-44).  Symbol order within a date: ``daily_weights.add(mgr_w_today * fac_w,
 fill_value=0)`` (:63) aligns the first-appearance ``all_symbols`` index with a manager's
 date-sorted book index; unless the two are identical pandas returns their sorted union,
@@ -26,7 +31,7 @@ import torch
 
 from . import engine as E
 from .panel import device, panel_index
-from .simulation import by_date, trade_books
+from .simulation import by_date, mvo_manager_books, mvo_runs_natively, mvo_turnover_runs_natively, trade_books
 
 logger = logging.getLogger("multi_manager")
 HOST_METHODS = ("mvo", "mvo_turnover")
@@ -56,6 +61,40 @@ def _host_books(pi, factors_df, mgrs, settings, dev):
     return torch.as_tensor(Wf, device=dev), torch.as_tensor(cnt, device=dev)
 
 
+def _mvo_settings(settings):
+    """The MVO fields of the settings, with SimulationSettings' defaults."""
+    return {k: _setting(settings, k, d) for k, d in (("returns", None), ("use_cvxpy", True), ("lookback_period", 60),
+                                                     ("shrinkage_intensity", 0.1), ("turnover_penalty", 0.1),
+                                                     ("return_weight", 0.0))}
+
+
+def _batched(method, factors_df, mgrs, settings) -> bool:
+    """Whether all managers' books of ``method`` come from ``mvo_manager_books``: the conditions
+    under which ``Simulation`` itself solves the method on the device."""
+    m = _mvo_settings(settings)
+    args = (factors_df[mgrs], m["returns"], m["use_cvxpy"], m["lookback_period"], m["shrinkage_intensity"])
+    if method == "mvo":
+        return mvo_runs_natively(*args)
+    return mvo_turnover_runs_natively(*args, m["turnover_penalty"], m["return_weight"])
+
+
+def _device_books(factors_df, mgrs, method, pct, max_weight, settings):
+    """All MVO managers' books in one device pass; the iteration-limit / x0 report of
+    ``Simulation._native_mvo_trade_list`` once for the batch."""
+    m = _mvo_settings(settings)
+    kw = {"turnover_penalty": float(m["turnover_penalty"]), "return_weight": float(m["return_weight"])} \
+        if method == "mvo_turnover" else {}
+    Wf, cnt, extra = mvo_manager_books(factors_df, mgrs, m["returns"], method, pct, max_weight, int(m["lookback_period"]),
+                                       float(m["shrinkage_intensity"]), return_info=True, **kw)
+    st = extra["info"][:, :, 0]
+    n1, n2 = int((st == 1).sum()), int((st == 2).sum())
+    if n1 or n2:
+        logger.warning("%s: of %d manager days over %d managers, %d stopped at the iteration limit (last iterate kept) "
+                       "and %d took the equal-leg fallback x0 (one-row window or max_weight too small for a leg)",
+                       method, int((st != 5).sum()), len(mgrs), n1, n2)
+    return Wf, cnt
+
+
 def compute_multimanager_weights(factors_df: pd.DataFrame, factor_weights: pd.DataFrame, settings):
     method = _setting(settings, "method", "equal")
     pct = float(_setting(settings, "pct", 0.1))
@@ -76,7 +115,9 @@ def compute_multimanager_weights(factors_df: pd.DataFrame, factor_weights: pd.Da
     pi = panel_index(factors_df.index)
     dev = device()
     F, D, A = len(mgrs), pi.D, pi.A
-    if F and method in HOST_METHODS:
+    if F and method in HOST_METHODS and _batched(method, factors_df, mgrs, settings):
+        Wf, cnt = _device_books(factors_df, mgrs, method, pct, max_weight, settings)
+    elif F and method in HOST_METHODS:
         Wf, cnt = _host_books(pi, factors_df, mgrs, settings, dev)
     elif F:
         Wf, cnt = trade_books(pi, factors_df[mgrs].to_numpy(dtype=np.float64), method, pct, max_weight, True)

@@ -34,7 +34,6 @@ from ``portfolio_analyzer`` when ``run()`` needs it.
 from __future__ import annotations
 
 import logging
-import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -44,7 +43,8 @@ import torch
 from . import _refload
 from . import engine as E
 from .panel import device
-from .simulation import daily_trade_list, mvo_trade_list, mvo_turnover_trade_list
+from .simulation import (daily_trade_list, mvo_runs_natively, mvo_trade_list, mvo_turnover_runs_natively,
+                         mvo_turnover_trade_list)
 
 RESULT_COLS = ["log_return", "long_return", "short_return", "long_turnover", "short_turnover", "turnover"]
 
@@ -188,33 +188,19 @@ class Simulation:
         symbols, a lookback outside 1..64, a shrinkage intensity above 1) or not two unique
         (date, symbol) indexes.  ``mvo_solver`` only selects among cvxpy back ends for the
         same QP and is ignored."""
-        if not self.use_cvxpy or os.environ.get("FMX_SIM_MVO", "").lower() == "reference":
+        if not isinstance(self.custom_feature, pd.Series):
             return False
-        if not torch.cuda.is_available():
-            return False
-        f, r = self.custom_feature, self.returns
-        if not (isinstance(f, pd.Series) and isinstance(r, pd.Series)):
-            return False
-        for idx in (f.index, r.index):
-            if not isinstance(idx, pd.MultiIndex) or idx.nlevels != 2 or not idx.is_unique:
-                return False
-        if not 1 <= int(self.lookback_period) <= E.SIM_MVO_MAX_T or not self.shrinkage_intensity <= 1.0:
-            return False
-        return f.index.get_level_values(1).nunique() <= E.SIM_MVO_MAX_A
+        return mvo_runs_natively(self.custom_feature, self.returns, self.use_cvxpy, self.lookback_period,
+                                 self.shrinkage_intensity)
 
     def _mvo_turnover_runs_natively(self) -> bool:
         """'mvo_turnover' stays the reference's host loop unless ``FMX_SIM_MVO_TURNOVER=native``
         is set; then it runs on the device under the conditions of ``_mvo_runs_natively``, with
         a ``turnover_penalty`` >= 0 and a finite ``return_weight``."""
-        if os.environ.get("FMX_SIM_MVO_TURNOVER", "").lower() != "native":
+        if not isinstance(self.custom_feature, pd.Series):
             return False
-        try:
-            tau, r = float(self.turnover_penalty), float(self.return_weight)
-        except (TypeError, ValueError):
-            return False
-        if not (tau >= 0.0 and np.isfinite(tau) and np.isfinite(r)):
-            return False
-        return self._mvo_runs_natively()
+        return mvo_turnover_runs_natively(self.custom_feature, self.returns, self.use_cvxpy, self.lookback_period,
+                                          self.shrinkage_intensity, self.turnover_penalty, self.return_weight)
 
     def _native_mvo_turnover_trade_list(self):
         """portfolio_simulation.py:96-154 with :206-248, :463-585

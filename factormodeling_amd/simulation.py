@@ -18,8 +18,18 @@ and days without any returns history take the equal-weight book (:188-190).
 the previous day's book.  ``k_smt_setup`` prepares every date at once and ``k_smt_chain``
 walks the dates in order on the device (csrc/sim_mvo_turnover.hip); the drop-in
 ``Simulation`` routes to it when ``FMX_SIM_MVO_TURNOVER=native`` is set.
+
+``mvo_manager_books(factors_df, cols, returns, method, ...)`` is the books of ALL the MVO
+managers of ``multi_manager.compute_multimanager_weights`` in one device pass: manager f is
+``factors_df[cols[f]].dropna()``, with its own windows (``engine.sim_mvo_window_rows``) and, for
+'mvo_turnover', its own date list (``engine.sim_mvo_turnover_chains``, one chain per manager).
+
+``mvo_runs_natively`` / ``mvo_turnover_runs_natively`` are the conditions under which the MVO
+methods run on the device, shared by ``Simulation`` and ``multi_manager``.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import pandas as pd
@@ -215,3 +225,140 @@ def mvo_trade_list(custom_feature: pd.Series, returns: pd.Series, pct: float = 0
         return shifted, counts_df, {"info": info.cpu().numpy(), "books": W.cpu().numpy(), "dates": pi.dates,
                                     "symbols": pi.symbols}
     return shifted, counts_df
+
+
+# ----------------------------------------------------------------------------- routing
+def mvo_runs_natively(feature, returns, use_cvxpy, lookback_period, shrinkage_intensity) -> bool:
+    """'mvo' solves every date's QP on the device unless the caller asked for the host SLSQP
+    solver (``use_cvxpy=False``) or the reference (``FMX_SIM_MVO=reference``), no GPU is
+    visible, or the inputs are outside the kernel's caps (more than 16,384 symbols, a lookback
+    outside 1..64, a shrinkage intensity above 1) or not two unique (date, symbol) indexes.
+    ``feature`` is one manager's Series or the managers' DataFrame, ``returns`` a Series."""
+    if not use_cvxpy or os.environ.get("FMX_SIM_MVO", "").lower() == "reference":
+        return False
+    if not torch.cuda.is_available():
+        return False
+    if not (isinstance(feature, (pd.Series, pd.DataFrame)) and isinstance(returns, pd.Series)):
+        return False
+    for idx in (feature.index, returns.index):
+        if not isinstance(idx, pd.MultiIndex) or idx.nlevels != 2 or not idx.is_unique:
+            return False
+    try:
+        if not 1 <= int(lookback_period) <= E.SIM_MVO_MAX_T or not shrinkage_intensity <= 1.0:
+            return False
+    except (TypeError, ValueError):
+        return False
+    return feature.index.get_level_values(1).nunique() <= E.SIM_MVO_MAX_A
+
+
+def mvo_turnover_runs_natively(feature, returns, use_cvxpy, lookback_period, shrinkage_intensity, turnover_penalty,
+                               return_weight) -> bool:
+    """'mvo_turnover' stays the reference's host loop unless ``FMX_SIM_MVO_TURNOVER=native`` is
+    set; then it runs on the device under the conditions of ``mvo_runs_natively``, with a
+    ``turnover_penalty`` >= 0 and a finite ``return_weight``."""
+    if os.environ.get("FMX_SIM_MVO_TURNOVER", "").lower() != "native":
+        return False
+    try:
+        tau, r = float(turnover_penalty), float(return_weight)
+    except (TypeError, ValueError):
+        return False
+    if not (tau >= 0.0 and np.isfinite(tau) and np.isfinite(r)):
+        return False
+    return mvo_runs_natively(feature, returns, use_cvxpy, lookback_period, shrinkage_intensity)
+
+
+# ----------------------------------------------------------------------------- all managers at once
+MM_CHUNK_BYTES = 4 << 30      # device tensors of one chunk of managers in mvo_manager_books
+
+
+def _manager_bytes(method, D, A, Lmax):
+    """Device bytes one manager needs in ``mvo_manager_books``: X, W, the equal-weight pair and
+    the shifted book ([D][A] doubles), the presence mask, the window tables and, for
+    'mvo_turnover', the chain kernel's workspace slot per date."""
+    per_date = A * (5 * 8 + 1) + 4 * (Lmax + 1) + 8 * 8
+    if method == "mvo_turnover":
+        per_date += 8 * (16 + Lmax * Lmax)
+    return D * per_date
+
+
+def mvo_manager_books(factors_df: pd.DataFrame, cols, returns: pd.Series, method: str, pct: float = 0.1,
+                      max_weight: float = 0.03, lookback_period: int = 60, shrinkage_intensity: float = 0.1,
+                      turnover_penalty: float = 0.1, return_weight: float = 0.0, max_iter: int = 20000,
+                      eps: float = 1e-9, return_info: bool = False, chunk_bytes: int = None):
+    """The books of the managers ``cols`` of ``compute_multimanager_weights`` for ``method``
+    'mvo' or 'mvo_turnover': (Wf [F][D][A] per-symbol-shifted books, NaN = no row; cnt [F][D][2]
+    counts, NaN = no book that date) on the device, on ``panel_index(factors_df.index)``'s grid.
+    Manager f is ``Simulation._daily_trade_list`` over ``factors_df[cols[f]].dropna()``: a cell
+    is a row of manager f when the frame has the row and the value is not NaN, and a date on
+    which manager f has no row is not one of its dates (the turnover chain's previous book is
+    the one of its last date with rows).  The returns panel goes up once; every (manager, date)
+    gets its own window (``engine.sim_mvo_window_rows``); 'mvo' is one ``engine.sim_mvo_books``
+    launch over the F * D rows, 'mvo_turnover' one chain per manager
+    (``engine.sim_mvo_turnover_chains``); dates without returns history carry the batched
+    equal-weight book.  Managers are processed in chunks of at most ``chunk_bytes`` (default
+    ``MM_CHUNK_BYTES``) of device tensors; every manager is independent of the others, so the
+    results do not depend on the chunking.  With ``return_info`` a third value holds ``info``
+    [F][D][6] (status 5: not a date of the manager), the same-day ``books`` [F][D][A] and, for
+    'mvo_turnover', the solver's ``opt`` [F][D][A], as numpy arrays."""
+    if method not in ("mvo", "mvo_turnover"):
+        raise NotImplementedError(f"method {method!r}: mvo_manager_books runs 'mvo' and 'mvo_turnover'")
+    factors_df = by_date(factors_df)
+    cols = list(cols)
+    dev = device()
+    pi = panel_index(factors_df.index)
+    F, D, A = len(cols), pi.D, pi.A
+    rdates, rd, rs, keep = _returns_grid(pi, returns)
+    Dr = len(rdates)
+    r0 = np.zeros((max(Dr, 1), A))
+    rv = returns.to_numpy(dtype=np.float64, na_value=np.nan)[keep]
+    r0[rd[keep], rs[keep]] = np.where(np.isnan(rv), 0.0, rv)                                  # fillna(0), :337
+    rp = np.zeros((Dr, A), dtype=np.uint8)
+    rp[rd[keep], rs[keep]] = 1
+    R0, RP = torch.as_tensor(r0, device=dev), torch.as_tensor(rp, device=dev)
+    nbefore = torch.as_tensor(np.searchsorted(rdates, np.asarray(pi.dates), side="left").astype(np.int32), device=dev)
+    Lmax = max(1, min(int(lookback_period), Dr))
+    budget = MM_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    Fc = max(1, min(F, budget // max(1, _manager_bytes(method, D, A, Lmax))))
+    Wf = torch.empty((F, D, A), dtype=torch.float64, device=dev)
+    cnt = torch.empty((F, D, 2), dtype=torch.float64, device=dev)
+    keep_info = {"info": [], "books": [], "opt": []}
+    for f0 in range(0, F, Fc):
+        X = pi.to_device(factors_df[cols[f0:f0 + Fc]].to_numpy(dtype=np.float64), dev)           # [n][D][A], NaN = no row
+        n = X.shape[0]
+        has_rows = (X == X).any(dim=2)                                                       # [n][D]
+        pres = (X == X).to(torch.uint8)
+        win_rows, win_T = E.sim_mvo_window_rows(pres.reshape(n * D, A), RP, nbefore.repeat(n), lookback_period)
+        _, ce, we = E.trade_books(X, "equal", pct, max_weight, present=pi.present(dev), nan_absent=True, raw=True)
+        if method == "mvo":
+            W, counts, info = E.sim_mvo_books(R0, win_rows, win_T, X.reshape(n * D, A), pres.reshape(n * D, A),
+                                              shrinkage_intensity, max_weight, max_iter, eps)
+            W, counts, info = W.reshape(n, D, A), counts.reshape(n, D, 2), info.reshape(n, D, 6)
+            Wopt = None
+            eq = (info[:, :, 0] == 4) & has_rows
+            W[eq] = we[eq]
+            info[:, :, 0][~has_rows] = 5.0
+        else:
+            win_rows, win_T = win_rows.reshape(n, D, -1), win_T.reshape(n, D)
+            W = torch.zeros_like(X)
+            eq = (win_T == 0) & has_rows
+            W[eq] = we[eq]
+            out = E.sim_mvo_turnover_chains(R0, win_rows, win_T, X, pres, W, shrinkage_intensity, max_weight,
+                                            turnover_penalty, return_weight, max_iter, eps, skip_absent=True,
+                                            return_opt=return_info)
+            W, counts, info = out[:3]
+            Wopt = out[3] if return_info else None
+            eq = info[:, :, 0] == 4
+        counts[eq] = ce[eq]
+        counts[~has_rows] = float("nan")
+        Wf[f0:f0 + n] = E.shift_rows(W)
+        cnt[f0:f0 + n] = counts
+        if return_info:
+            keep_info["info"].append(info.cpu().numpy())
+            keep_info["books"].append(W.cpu().numpy())
+            if Wopt is not None:
+                keep_info["opt"].append(Wopt.cpu().numpy())
+    if return_info:
+        extra = {k: np.concatenate(v) for k, v in keep_info.items() if v}
+        extra.update(dates=pi.dates, symbols=pi.symbols)
+        return Wf, cnt, extra
+    return Wf, cnt

@@ -539,6 +539,39 @@ fmx_status fmx_sim_mvo_turnover_books(const double* R0, int64_t Dr, int64_t A, c
                                       double turnover_penalty, double return_weight, int32_t max_iter, double eps,
                                       double* W, double* Wopt, double* counts, double* info, void* work,
                                       int64_t work_bytes, void* stream);
+/* fmx_sim_mvo_turnover_books with per-chain window tables and per-chain date lists: the B
+ * chains are the managers of multi_manager.compute_multimanager_weights, each over its own
+ * dropna() rows of one (date, symbol) grid.
+ *   win_rows [.][Lmax], win_T [.]: win_stride is the number of table rows between two chains'
+ *     tables -- 0: one [J] table shared by the chains, J: [B][J] tables, chain b's date j at
+ *     row b * J + j.  Every row read is range-checked before the launch, as above.
+ *   skip_absent != 0: a (chain, date) without a present cell is not a date of that chain: its
+ *     W / Wopt row is NaN, its counts are NaN, info[0] = 5, and the chain's book is left as it
+ *     was, so the next date's p is the book of the last date on which the chain had rows
+ *     (the reference iterates the manager's own dates, portfolio_simulation.py:100, :206-225).
+ *     A date with one present row stays a flat day (status 3): its zero book is the next p.
+ *   skip_absent == 0 and win_stride == 0 are fmx_sim_mvo_turnover_books, bit for bit.
+ * work: fmx_sim_mvo_turnover_chains_work_bytes(A, Lmax, J, B) bytes. */
+int64_t fmx_sim_mvo_turnover_chains_work_bytes(int64_t A, int64_t Lmax, int64_t J, int64_t B);
+fmx_status fmx_sim_mvo_turnover_chains(const double* R0, int64_t Dr, int64_t A, const int32_t* win_rows,
+                                       const int32_t* win_T, int64_t Lmax, int64_t win_stride, const double* X,
+                                       const uint8_t* present, int64_t J, int64_t B, double shrinkage,
+                                       double max_weight, double turnover_penalty, double return_weight,
+                                       int32_t max_iter, double eps, int32_t skip_absent, double* W, double* Wopt,
+                                       double* counts, double* info, void* work, int64_t work_bytes, void* stream);
+/* The returns windows of N (manager, date) rows (portfolio_simulation.py:319-334;
+ * csrc/sim_mvo_windows.hip): row n's window is the last Lmax returns dates r < nbefore[n] on
+ * which at least one symbol present in fpresent[n] has a returns row.
+ *   fpresent [N][A], rpresent [Dr][A] (uint8, nonzero = present; rpresent may be NULL when
+ *   Dr = 0), nbefore [N] (device int32): the number of returns dates before the row's date,
+ *   0 <= nbefore <= Dr (read back and checked: FMX_ERR_ARG otherwise);
+ *   win_rows [N][Lmax] ascending, the unused tail 0; win_T [N] the window lengths.
+ * 1 <= A <= 16384, 1 <= Lmax <= 64.  work: fmx_sim_mvo_window_rows_work_bytes(N, A, Dr) bytes
+ * (both masks packed to 64-bit words). */
+int64_t fmx_sim_mvo_window_rows_work_bytes(int64_t N, int64_t A, int64_t Dr);
+fmx_status fmx_sim_mvo_window_rows(const uint8_t* fpresent, const uint8_t* rpresent, const int32_t* nbefore,
+                                   int64_t N, int64_t A, int64_t Dr, int64_t Lmax, int32_t* win_rows, int32_t* win_T,
+                                   void* work, int64_t work_bytes, void* stream);
 
 /* ---- portfolio P&L (portfolio_simulation.py:748-819) ---------- */
 /* Replaces Simulation._daily_portfolio_returns' per-date sums on the aligned [D][A] grid
