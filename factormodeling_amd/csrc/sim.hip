@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <algorithm>
+#include <vector>
 #include "../../include/fmx.h"
 #include "fmx_common.hpp"
 #include "rowkit.hpp"
@@ -601,6 +602,90 @@ k_pnl_daily(const double* __restrict__ W, const double* __restrict__ R, const do
   if (threadIdx.x < 6) out[d * 6 + threadIdx.x] = acc[threadIdx.x];
 }
 
+// The six sums of k_pnl_daily for F books in one launch (fmx_pnl_books).  Wraw [F][D][A] holds
+// the SAME-DAY books; the per-symbol shift(1) is folded into the read: the shifted weight of
+// cell (d, a) is Wraw[f][prev_row[d][a]][a] (0 for -1), so no shifted copy exists.  One
+// workgroup per (date, tile of PB_TF books): r, the cap rate and the two previous-row entries
+// (the date's own and the previous weights date's) are loaded once per cell and reused
+// across the tile.  Per (book, date) the summation schedule is k_pnl_daily's -- lane t adds
+// cells t, t + 256, ... in order, the xor-shuffle tree, the wave partials in wave order --
+// so out[f] carries the bits of k_pnl_daily on the shifted book f.  Previous-row entries
+// outside [-1, d) are checked on the host before the launch; the kernel reads them as -1.
+constexpr int PB_TF = 4;
+__global__ void __launch_bounds__(PNL_NT)
+k_pnl_books(const double* __restrict__ Wraw, const double* __restrict__ R, const double* __restrict__ CAP,
+            const int32_t* __restrict__ prev_row, const int32_t* __restrict__ wprev, double* __restrict__ out,
+            int64_t F, int64_t D, int64_t A) {
+  __shared__ double scr[PB_TF][(PNL_NT / 64) * 6];
+  const int64_t d = blockIdx.x, f0 = (int64_t)blockIdx.y * PB_TF;
+  int64_t pv = wprev[d];
+  if (pv < -1 || pv >= D) pv = -1;
+  const bool diff = pv >= 0;
+  const double* wf[PB_TF];
+#pragma unroll
+  for (int j = 0; j < PB_TF; ++j) {               // a tile past the last book re-reads book F - 1
+    const int64_t f = f0 + j < F ? f0 + j : F - 1;
+    wf[j] = Wraw + f * D * A;
+  }
+  const double* r = R + d * A;
+  const double* cp = CAP ? CAP + d * A : nullptr;
+  const int32_t* q0 = prev_row ? prev_row + d * A : nullptr;
+  const int32_t* q1 = (prev_row && diff) ? prev_row + pv * A : nullptr;
+  double acc[PB_TF][6];
+#pragma unroll
+  for (int j = 0; j < PB_TF; ++j)
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[j][i] = 0.0;
+  for (int64_t a = threadIdx.x; a < A; a += PNL_NT) {
+    const double rv = nz(r[a]);
+    int64_t p0 = q0 ? (int64_t)q0[a] : d - 1;
+    if (p0 < -1 || p0 >= d) p0 = -1;
+    int64_t p1 = -1;
+    double rate = 0.0;
+    if (diff) {
+      p1 = q1 ? (int64_t)q1[a] : pv - 1;
+      if (p1 < -1 || p1 >= pv) p1 = -1;
+      rate = cp ? cap_rate(cp[a]) : 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < PB_TF; ++j) {
+      const double wv = p0 >= 0 ? nz(wf[j][p0 * A + a]) : 0.0;
+      const double l = wv > 0.0 ? wv : 0.0, sh = wv < 0.0 ? -wv : 0.0;
+      acc[j][0] += l * rv;
+      acc[j][1] += sh * rv;
+      if (diff) {
+        const double pw = p1 >= 0 ? nz(wf[j][p1 * A + a]) : 0.0;
+        const double pl = pw > 0.0 ? pw : 0.0, ps = pw < 0.0 ? -pw : 0.0;
+        const double dl = fabs(l - pl), ds = fabs(sh - ps);
+        acc[j][2] += dl;
+        acc[j][3] += ds;
+        acc[j][4] += dl * rate;
+        acc[j][5] += ds * rate;
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < PB_TF; ++j) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      double v = acc[j][i];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      if (lane == 0) scr[j][wid * 6 + i] = v;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < PB_TF * 6) {
+    const int j = threadIdx.x / 6, i = threadIdx.x % 6;
+    if (f0 + j < F) {
+      double t = 0.0;
+      for (int w = 0; w < PNL_NT / 64; ++w) t += scr[j][w * 6 + i];
+      out[((f0 + j) * D + d) * 6 + i] = t;
+    }
+  }
+}
+
 // Per-symbol contributions (contributor=True, :790-793): column sums over the dates of
 // longs * r - |d longs| * rate (and the short leg with -shorts * r).  One lane per asset.
 __global__ void k_pnl_contrib(const double* __restrict__ W, const double* __restrict__ R,
@@ -682,6 +767,35 @@ extern "C" fmx_status fmx_pnl_daily(const double* W, const double* R, const doub
     k_pnl_contrib<<<(unsigned)ceil_div(A, 256), 256, 0, as_stream(stream)>>>(W, R, CAP, wprev, contrib, D, A);
     FMX_LAUNCH_CHECK("k_pnl_contrib");
   }
+  return FMX_OK;
+}
+
+extern "C" fmx_status fmx_pnl_books(const double* Wraw, const double* R, const double* CAP, const int32_t* prev_row,
+                                    const int32_t* wprev, double* out, int64_t F, int64_t D, int64_t A,
+                                    void* stream) {
+  FMX_ARG(Wraw && R && wprev && out && F >= 0 && D >= 0 && A >= 0, "pnl_books: bad args");
+  if (F == 0 || D == 0) return FMX_OK;
+  FMX_ARG(D <= 0x7fffffffll, "pnl_books: too many dates");
+  const int64_t gy = ceil_div(F, PB_TF);
+  FMX_ARG(gy <= 65535, "pnl_books: too many books for one call");
+  hipStream_t s = as_stream(stream);
+  // the row tables are read back and checked: an entry that does not point at an earlier row
+  // (or -1) is an argument error, not a fault
+  std::vector<int32_t> hw((size_t)D);
+  FMX_HIP(hipMemcpyAsync(hw.data(), wprev, sizeof(int32_t) * hw.size(), hipMemcpyDeviceToHost, s));
+  std::vector<int32_t> hp;
+  if (prev_row && A > 0) {
+    hp.resize((size_t)(D * A));
+    FMX_HIP(hipMemcpyAsync(hp.data(), prev_row, sizeof(int32_t) * hp.size(), hipMemcpyDeviceToHost, s));
+  }
+  FMX_HIP(hipStreamSynchronize(s));
+  for (int32_t v : hw) FMX_ARG(v >= -1 && v < D, "pnl_books: wprev entry outside [-1, D)");
+  for (size_t i = 0; i < hp.size(); ++i) {
+    const int64_t d = (int64_t)(i / (size_t)A);
+    FMX_ARG(hp[i] >= -1 && hp[i] < d, "pnl_books: prev_row entry outside [-1, d)");
+  }
+  k_pnl_books<<<dim3((unsigned)D, (unsigned)gy), PNL_NT, 0, s>>>(Wraw, R, CAP, prev_row, wprev, out, F, D, A);
+  FMX_LAUNCH_CHECK("k_pnl_books");
   return FMX_OK;
 }
 

@@ -1167,6 +1167,34 @@ def pnl_daily(W, R, CAP, wprev, contrib=False):
     return out, cb
 
 
+def pnl_books(Wraw, R, CAP, wprev, prev_row=None):
+    """The six per-date sums of ``pnl_daily`` for F books in one launch (fmx_pnl_books):
+    Wraw [F][D][A] SAME-DAY books (``trade_books(..., raw=True)``: NaN = no row), R / CAP
+    [D][A] and wprev [D] shared by the books, prev_row int32 [D][A] (each cell's previous
+    feature row of its symbol, -1 = none / not a feature row) or None for the dense grid
+    (row d - 1).  Returns out [F][D][6]; out[f] has the bits of
+    ``pnl_daily(shift_rows(Wraw)[f], R, CAP, wprev)[0]``."""
+    _check_panel(Wraw, "Wraw")
+    _dense2(R, "R")
+    F, D, A = Wraw.shape
+    if tuple(R.shape) != (D, A) or (CAP is not None and (tuple(CAP.shape) != (D, A))):
+        raise _lib.FmxError("pnl_books: shape mismatch")
+    if CAP is not None:
+        _dense2(CAP, "CAP")
+    wp = torch.as_tensor(np.ascontiguousarray(np.asarray(wprev, dtype=np.int32)), device=Wraw.device)
+    if wp.numel() != D:
+        raise _lib.FmxError("pnl_books: wprev must be [D] row indices < D (or -1)")
+    if prev_row is not None:
+        prev_row = torch.as_tensor(prev_row, dtype=torch.int32).to(Wraw.device).contiguous()
+        if tuple(prev_row.shape) != (D, A):
+            raise _lib.FmxError("pnl_books: prev_row must be int32 [D][A]")
+    out = torch.zeros((F, D, 6), dtype=F64, device=Wraw.device)
+    if Wraw.numel() == 0:
+        return out
+    call("fmx_pnl_books", ptr(Wraw), ptr(R), ptr(CAP), ptr(prev_row), ptr(wp), ptr(out), F, D, A, stream_ptr())
+    return out
+
+
 def daily_corr(X, R):
     """Per-date Pearson (np.corrcoef) of pair-valid cells (fmx_daily_corr): [D][2] = (n, corr)."""
     _dense2(X, "X")

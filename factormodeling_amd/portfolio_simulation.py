@@ -333,3 +333,6 @@ class Simulation:
             "Avg Turnover (%)": [turnover_series.mean() * 100]
         })
         return round(metrics, 2)
+
+
+from .factor_backtest import single_factor_backtests, single_factor_returns  # noqa: E402,F401  (all factors in one pass)

@@ -582,6 +582,20 @@ fmx_status fmx_sim_mvo_window_rows(const uint8_t* fpresent, const uint8_t* rpres
  * (optional) = per-symbol long / short P&L net of cost (contributor=True, :790-793). */
 fmx_status fmx_pnl_daily(const double* W, const double* R, const double* CAP, const int32_t* wprev, double* out,
                          double* contrib, int64_t D, int64_t A, void* stream);
+/* The six sums of fmx_pnl_daily (portfolio_simulation.py:748-797) for F books in one launch.
+ * Wraw [F][D][A] holds the SAME-DAY books (the raw output of fmx_trade_books: finite where
+ * the feature has a row, NaN elsewhere); the per-symbol shift(1) is folded into the read,
+ * so no shifted copy is made.  R, CAP (or NULL: no cost) [D][A] and wprev [D] are as in
+ * fmx_pnl_daily and shared by all books.
+ *   prev_row [D][A] (device int32), shared by all books: p >= 0 = the cell has a feature row
+ *     and its shifted weight is Wraw[f][p][a]; -1 = the shifted weight is 0 (no row, or the
+ *     symbol's first row); NULL = the dense grid (p = d - 1, -1 at d = 0).  The table and
+ *     wprev are read back before the launch: a prev_row entry outside [-1, d) or a wprev
+ *     entry outside [-1, D) is FMX_ERR_ARG.
+ * out [F][D][6]: out[f] holds the same bits as fmx_pnl_daily on book f of
+ * fmx_shift_rows(Wraw) (the same per-lane order, shuffle tree and wave order per date). */
+fmx_status fmx_pnl_books(const double* Wraw, const double* R, const double* CAP, const int32_t* prev_row,
+                         const int32_t* wprev, double* out, int64_t F, int64_t D, int64_t A, void* stream);
 /* Replaces _calculate_metrics' daily IC (:799-805): per date, Series.corr (np.corrcoef) of
  * the pair-valid (X, R) cells.  out [D][2] = (n, corr); corr NaN for n < 2 or constant. */
 fmx_status fmx_daily_corr(const double* X, const double* R, double* out, int64_t D, int64_t A, void* stream);
