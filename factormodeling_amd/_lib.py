@@ -84,6 +84,10 @@ SIGNATURES = {
     "fmx_gram_fused_work_bytes": [c_i64, c_i64, c_i64, c_i64, c_i64],
     "fmx_gram_exact": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp],
     "fmx_gram_exact_work_bytes": [c_i64, c_i64, c_i64, c_i64, c_i64],
+    "fmx_gram_exact_rows": [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_i64,
+                            c_vp],
+    "fmx_gram_exact_rows_work_bytes": [c_i64, c_i64, c_i64, c_i64, c_i64],
+    "fmx_prune_head": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_dbl, c_i64, c_vp, c_vp, c_vp, c_vp],
     "fmx_gram_exact_finalize": [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "fmx_gram_exact_units_per_date": [c_i64],
     "fmx_debug_exact_fold": [c_vp, c_i64, c_vp, c_vp],
@@ -121,6 +125,7 @@ _RESTYPES = {"fmx_last_error": c_cp, "fmx_build_variant": c_cp, "fmx_ic_ranked_w
              "fmx_group_op_long_work_bytes": c_i64,
              "fmx_gram_fused_work_bytes": c_i64, "fmx_corr_prune_windows_work_bytes": c_i64,
              "fmx_cs_rank_sorted_work_bytes": c_i64, "fmx_group_rank_sorted_work_bytes": c_i64, "fmx_gram_exact_work_bytes": c_i64,
+             "fmx_gram_exact_rows_work_bytes": c_i64,
              "fmx_mvo_windows_work_bytes": c_i64, "fmx_sim_mvo_books_work_bytes": c_i64,
              "fmx_sim_mvo_turnover_books_work_bytes": c_i64, "fmx_sim_mvo_turnover_chains_work_bytes": c_i64,
              "fmx_sim_mvo_window_rows_work_bytes": c_i64,

@@ -972,6 +972,159 @@ static fmx_status gram_exact_launch(const double* X, const double* stats, int64_
 }
 
 // ---------------------------------------------------------------------------------------
+// Head-block Gram (fmx_gram_exact_rows): k_gram_db<NB, true, true>'s unit partials for the
+// H <= 64 panel rows a device index list names (the head of the prune order), read in place.
+// Same units, 32-asset chunks, k map and one MFMA chain per unit, so a pair's partials --
+// and their exact fold -- are the bits the full kernel gives that factor pair (with the A
+// and B roles swapped where the list inverts the pair: the products commute).  The regime
+// is the opposite of k_gram_db's: 3 of 96 MFMA blocks at H = 32, so the kernel is bound by
+// the panel read, not the matrix cores.  Hence 256-thread workgroups, several per CU (17 KB
+// of LDS at NB = 2), each with two chunks of loads in flight in registers (x0 / x1) behind
+// the chunk being staged: ~16 KB per workgroup, 64-128 KB per CU.
+constexpr int GR_NT = 256;
+template <int NB>
+__global__ void __launch_bounds__(GR_NT)
+k_gram_rows(const double* __restrict__ X, const int64_t* __restrict__ rows, int64_t H, int64_t F, int64_t D,
+            int64_t A, int64_t ld, int64_t d0, int64_t nch, int64_t total, int64_t nslice,
+            double* __restrict__ part, uint32_t* __restrict__ mbits, int units_per_date) {
+  constexpr int FP = 16 * NB;
+  constexpr int NTRI = NB * (NB + 1) / 2;
+  constexpr int NWV = GR_NT / 64;
+  constexpr int BPW = (NTRI + NWV - 1) / NWV;
+  constexpr int EPT = FP * SG_K / GR_NT;            // 2 NB rows per thread, GR_NT / 32 apart
+  __shared__ double Zs[2][FP * SG_KP];
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int64_t slice = blockIdx.x;
+  const int S = units_per_date;
+  const int64_t u0 = slice * total / nslice, u1 = (slice + 1) * total / nslice;
+  const int64_t c0 = unit_chunk(u0, S, nch), c1 = unit_chunk(u1, S, nch);
+  if (c0 >= c1) return;
+  int64_t cur_u = u0, u_end = unit_chunk(u0 + 1, S, nch);
+  int blk[BPW];                                     // as k_gram_db: BPW consecutive triangle blocks
+#pragma unroll
+  for (int u = 0; u < BPW; ++u) {
+    int j = BPW * wid + u, bi = 0;
+    blk[u] = -1;
+    if (j < NTRI) {
+      while (j >= NB - bi) { j -= NB - bi; ++bi; }
+      blk[u] = bi | ((bi + j) << 8);
+    }
+  }
+  dbl4 gacc[BPW];
+#pragma unroll
+  for (int u = 0; u < BPW; ++u) gacc[u] = dbl4{0.0, 0.0, 0.0, 0.0};
+  // this thread's rows: list positions r0 + 8 u; the panel offset of the row's date 0, or
+  // -1 for a position past the list or an index outside [0, F) (an all-invalid row)
+  const int r0 = tid >> 5, cl = tid & 31;
+  int64_t rofs[EPT];
+#pragma unroll
+  for (int u = 0; u < EPT; ++u) {
+    const int r = r0 + (GR_NT / 32) * u;
+    const int64_t f = r < H ? rows[r] : -1;
+    rofs[u] = (f >= 0 && f < F) ? f * D * ld : -1;
+  }
+  int64_t ld_d = c0 / nch, ld_a = c0 - (c0 / nch) * nch;     // next chunk to load
+  auto issue = [&](double (&xr)[EPT]) {
+    const int64_t a = ld_a * SG_K + cl, o = (d0 + ld_d) * ld + a;
+    if (++ld_a == nch) { ld_a = 0; ++ld_d; }
+#pragma unroll
+    for (int u = 0; u < EPT; ++u) xr[u] = (rofs[u] >= 0 && a < A) ? X[rofs[u] + o] : qnan();
+  };
+  auto stage = [&](const double (&xr)[EPT], int64_t c, int b) {
+#pragma unroll
+    for (int u = 0; u < EPT; ++u) {
+      const int r = r0 + (GR_NT / 32) * u;
+      const double v = xr[u];
+      const bool ok = (v - v) == 0.0;               // finite z-score; NaN / +-inf -> invalid
+      Zs[b][r * SG_KP + cl] = ok ? v : 0.0;
+      const uint64_t bal = __ballot(ok);
+      if ((lane & 31) == 0 && r < H) mbits[(uint32_t)c * (uint32_t)H + (uint32_t)r] = (uint32_t)(bal >> lane);
+    }
+  };
+  double x0[EPT], x1[EPT];
+  // chunk c's iteration: Zs[b] holds c; xs holds c + 1 (staged now, then refilled with c + 3),
+  // the other register set c + 2
+  auto body = [&](int64_t c, double (&xs)[EPT]) {
+    const int b = (int)((c - c0) & 1);
+    if (c + 1 < c1) {
+      stage(xs, c + 1, b ^ 1);                      // that buffer was last read in chunk c - 1
+      if (c + 3 < c1) issue(xs);
+    }
+#pragma unroll 1
+    for (int ks = 0; ks < SG_K; ks += 8) {          // k_gram_db's k-steps, operand for operand
+      const int kk = ks + 2 * (lane >> 4);
+      int abi = -1;
+      dbl2 a = dbl2{0.0, 0.0};
+#pragma unroll
+      for (int u = 0; u < BPW; ++u) {
+        const int bk = blk[u] < 0 ? 0 : blk[u];     // no block: (0, 0) into an accumulator never stored
+        const int bi = bk & 0xff, bj = bk >> 8;
+        if (bi != abi) {
+          a = *reinterpret_cast<const dbl2*>(&Zs[b][(bi * 16 + (lane & 15)) * SG_KP + kk]);
+          abi = bi;
+        }
+        const dbl2 bb = *reinterpret_cast<const dbl2*>(&Zs[b][(bj * 16 + (lane & 15)) * SG_KP + kk]);
+        gacc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, bb.x, gacc[u], 0, 0, 0);
+        gacc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, bb.y, gacc[u], 0, 0, 0);
+      }
+    }
+    while (c + 1 == u_end) {                        // unit cur_u complete
+      double* pu = part + (cur_u * NTRI) * 256 + lane * 4;
+#pragma unroll
+      for (int u = 0; u < BPW; ++u) {
+        if (blk[u] < 0) continue;
+        *reinterpret_cast<dbl4*>(pu + (int64_t)(BPW * wid + u) * 256) = gacc[u];
+        gacc[u] = dbl4{0.0, 0.0, 0.0, 0.0};
+      }
+      if (++cur_u >= u1) break;
+      u_end = unit_chunk(cur_u + 1, S, nch);
+    }
+    __syncthreads();
+  };
+  issue(x0);
+  if (c0 + 1 < c1) issue(x1);
+  stage(x0, c0, 0);
+  if (c0 + 2 < c1) issue(x0);
+  __syncthreads();
+  for (int64_t c = c0; c < c1; c += 2) {
+    body(c, x1);
+    if (c + 1 < c1) body(c + 1, x0);
+  }
+}
+
+template <int NB>
+static fmx_status gram_rows_launch(const double* X, const int64_t* rows, int64_t H, int64_t* limbs, int64_t* counts,
+                                   int64_t F, int64_t D, int64_t A, int64_t ld, int64_t d0, int64_t d1, char* work,
+                                   hipStream_t st) {
+  constexpr int FP = 16 * NB;
+  const ExactPlan pl = exact_plan(H, A, d0, d1);
+  if (pl.nunits == 0 || A == 0) return FMX_OK;
+  FMX_ARG(pl.nw * H < ((int64_t)1 << 32), "panel too large for 32-bit validity-word indices");
+  double* part = reinterpret_cast<double*>(work);
+  uint32_t* mbits = reinterpret_cast<uint32_t*>(work + pl.part_bytes());
+  unsigned long long* ncnt = reinterpret_cast<unsigned long long*>(work + pl.part_bytes() + pl.bits_bytes());
+  FMX_HIP(hipMemsetAsync(ncnt, 0, pl.cnt_bytes(), st));
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      n = 256;
+    return std::max(n, 1);
+  }();
+  // equal unit ranges, ~8 workgroups per CU (the units are independent: any cut gives the same partials)
+  const int64_t nslice = std::max<int64_t>(1, std::min<int64_t>(pl.nunits, (int64_t)8 * cus));
+  k_gram_rows<NB><<<(unsigned)nslice, GR_NT, 0, st>>>(X, rows, H, F, D, A, ld, d0, pl.nch, pl.nunits, nslice, part,
+                                                     mbits, (int)pl.S);
+  FMX_LAUNCH_CHECK("k_gram_rows");
+  if (fmx_status e = launch_pair_counts_cm(mbits, H, pl.nw, FP, ncnt, st)) return e;
+  const int64_t ngroups = std::max<int64_t>(1, std::min<int64_t>(pl.nunits, 2048 / pl.ntri));
+  const int64_t upg = ceil_div(pl.nunits, ngroups);
+  k_gram_fold<<<dim3((unsigned)pl.ntri, (unsigned)ceil_div(pl.nunits, upg)), 256, 0, st>>>(
+      part, pl.nunits, upg, NB, H, limbs, ncnt, FP, counts);
+  FMX_LAUNCH_CHECK("k_gram_fold");
+  return FMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // Rolling correlation pruning (the builder-defined corr_prune selector, SURVEY A19, run for
 // every processed day of FactorSelector): window j pools the per-date Gram partials of the
 // raw dates [s0[j], s0[j] + W) -- the lag-1 factors of the window's dates -- and walks the
@@ -1053,6 +1206,49 @@ k_greedy_prune(const double* __restrict__ C, int64_t F, int64_t ldc, const int64
     __syncthreads();
   }
   if (tid == 0) *n_kept = (int32_t)nk;
+}
+
+// The prune from a head block (fmx_prune_head): k_gram_finalize's G, N of the H x H head
+// limbs / counts, C = N > 0 ? G / N : 0 into LDS (both triangles), then k_greedy_prune's
+// walk by position over the head.  One workgroup, H <= 64.
+constexpr int PH_MAX = 64, PH_NT = 256;
+__global__ void __launch_bounds__(PH_NT)
+k_prune_head(const int64_t* __restrict__ limbs, const int64_t* __restrict__ counts,
+             const int64_t* __restrict__ order, int H, int64_t n_order, int64_t F, double rho, int64_t top_x,
+             int32_t* __restrict__ kept, int32_t* __restrict__ n_kept, int32_t* __restrict__ done) {
+  __shared__ double Cs[PH_MAX * PH_MAX];
+  __shared__ double mx[PH_MAX];
+  const int tid = threadIdx.x, HH = H * H;
+  for (int e = tid; e < HH; e += PH_NT) {
+    const int i = e / H, j = e % H;
+    if (i > j) continue;
+    int64_t acc[EX_SLOTS];
+#pragma unroll
+    for (int k = 0; k < EX_SLOTS; ++k) acc[k] = limbs[(int64_t)k * HH + e];
+    const double g = ex_value(acc), n = (double)counts[e];
+    const double c = n > 0.0 ? g / n : 0.0;
+    Cs[i * H + j] = c;
+    Cs[j * H + i] = c;
+  }
+  if (tid < H) mx[tid] = -__builtin_inf();
+  __syncthreads();
+  const int hn = (int)min<int64_t>(H, n_order);
+  int64_t nk = 0;
+  for (int pos = 0; pos < hn && nk < top_x; ++pos) {
+    const int64_t c = order[pos];                  // block-uniform
+    if (c < 0 || c >= F) continue;
+    const double m = mx[pos];
+    if (m == m && m >= rho) continue;
+    if (tid == 0) kept[nk] = (int32_t)c;
+    ++nk;
+    __syncthreads();                               // all threads have read mx[pos]
+    if (tid < H) mx[tid] = gp_max(mx[tid], fabs(Cs[pos * H + tid]));
+    __syncthreads();
+  }
+  if (tid == 0) {
+    *n_kept = (int32_t)nk;
+    *done = (nk == top_x || (int64_t)H >= n_order) ? 1 : 0;
+  }
 }
 
 // Workspace of fmx_corr_prune_windows: per-date G and N partials over the dates the
@@ -1176,6 +1372,52 @@ extern "C" fmx_status fmx_gram_exact(const double* X, const double* stats, int64
 #undef FMX_GE
     default: return FMX_ERR_UNSUPPORTED;
   }
+}
+
+extern "C" int64_t fmx_gram_exact_rows_work_bytes(int64_t H, int64_t D, int64_t A, int64_t d0, int64_t d1) {
+  (void)D;
+  if (H <= 0 || H > 64 || d1 <= d0 || A <= 0) return 0;
+  return exact_plan(H, A, d0, d1).bytes();
+}
+
+extern "C" fmx_status fmx_gram_exact_rows(const double* Z, const int64_t* rows, int64_t H, int64_t* limbs,
+                                          int64_t* counts, int64_t F, int64_t D, int64_t A, int64_t ld, int64_t d0,
+                                          int64_t d1, int32_t accumulate, void* work, int64_t work_bytes,
+                                          void* stream) {
+  FMX_ARG(Z && limbs && counts && (rows || H == 0), "null pointer");
+  FMX_ARG(H >= 0 && F >= 0 && D >= 0 && A >= 0 && ld >= A && d0 >= 0 && d1 <= D && d0 <= d1, "bad dims");
+  if (H > 64) {
+    set_error("fmx_gram_exact_rows supports H <= 64 rows; use fmx_gram_exact");
+    return FMX_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = as_stream(stream);
+  if (!accumulate && H > 0) {
+    FMX_HIP(hipMemsetAsync(limbs, 0, sizeof(int64_t) * FMX_GRAM_EXACT_SLOTS * H * H, st));
+    FMX_HIP(hipMemsetAsync(counts, 0, sizeof(int64_t) * H * H, st));
+  }
+  if (H == 0 || d1 == d0 || A == 0) return FMX_OK;
+  if (fmx_status e = check_work(work, work_bytes, fmx_gram_exact_rows_work_bytes(H, D, A, d0, d1),
+                                "fmx_gram_exact_rows_work_bytes"))
+    return e;
+  char* w = static_cast<char*>(work);
+  switch ((int)ceil_div(H, 16)) {
+#define FMX_GR(K) \
+  case K: return gram_rows_launch<K>(Z, rows, H, limbs, counts, F, D, A, ld, d0, d1, w, st);
+    FMX_GR(1) FMX_GR(2) FMX_GR(3) FMX_GR(4)
+#undef FMX_GR
+    default: return FMX_ERR_UNSUPPORTED;
+  }
+}
+
+extern "C" fmx_status fmx_prune_head(const int64_t* limbs, const int64_t* counts, const int64_t* order, int64_t H,
+                                     int64_t n_order, int64_t F, double rho, int64_t top_x, int32_t* kept,
+                                     int32_t* n_kept, int32_t* done, void* stream) {
+  FMX_ARG(limbs && counts && order && kept && n_kept && done, "null pointer");
+  FMX_ARG(H >= 1 && H <= PH_MAX && n_order >= 0 && F >= 0 && top_x >= 1, "bad dims (1 <= H <= 64, top_x >= 1)");
+  k_prune_head<<<1, PH_NT, 0, as_stream(stream)>>>(limbs, counts, order, (int)H, n_order, F, rho, top_x, kept, n_kept,
+                                                   done);
+  FMX_LAUNCH_CHECK("k_prune_head");
+  return FMX_OK;
 }
 
 extern "C" fmx_status fmx_gram_exact_finalize(const int64_t* limbs, const int64_t* counts, double* G, double* N,

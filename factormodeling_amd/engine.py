@@ -614,7 +614,61 @@ def gram_exact_finalize(limbs, counts):
     return G, N
 
 
-GRAM_CHUNK_BYTES = 8 << 30      # Z + M workspace of one date chunk of the wide Gram
+GRAM_HEAD_MAX = 64              # fmx_gram_exact_rows / fmx_prune_head: rows of a head block
+
+
+def gram_exact_rows(Z, rows, d0=0, d1=None, limbs=None, counts=None, accumulate=False):
+    """gram_exact of the z-score panel ``Z`` restricted to the rows the device index list
+    ``rows`` (int64 [H], H <= 64) names, read in place (fmx_gram_exact_rows): (limbs int64
+    [7][H][H], counts int64 [H][H]) by position in the list, each entry the bits gram_exact
+    gives that factor pair.  An index outside [0, F) is an all-invalid row.  The host never
+    reads ``rows``: no sync."""
+    Z = as3(Z)
+    _check_panel(Z)
+    F, D, A = Z.shape
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64 or rows.dim() != 1 or rows.device != Z.device \
+            or not rows.is_contiguous():
+        raise _lib.FmxError("gram_exact_rows: rows must be a contiguous int64 [H] tensor on the panel's device")
+    H = int(rows.numel())
+    if not 1 <= H <= GRAM_HEAD_MAX:
+        raise _lib.FmxError(f"gram_exact_rows: 1 <= H <= {GRAM_HEAD_MAX}")
+    d1 = D if d1 is None else d1
+    if limbs is None:
+        limbs = torch.empty((GRAM_EXACT_SLOTS, H, H), dtype=torch.int64, device=Z.device)
+    if counts is None:
+        counts = torch.empty((H, H), dtype=torch.int64, device=Z.device)
+    if tuple(limbs.shape) != (GRAM_EXACT_SLOTS, H, H) or limbs.dtype != torch.int64 or not limbs.is_contiguous() \
+            or tuple(counts.shape) != (H, H) or counts.dtype != torch.int64 or not counts.is_contiguous():
+        raise _lib.FmxError("gram_exact_rows: limbs int64 [7][H][H], counts int64 [H][H]")
+    nb = int(_lib.load().fmx_gram_exact_rows_work_bytes(H, D, A, int(d0), int(d1)))
+    work, wb = _workspace_bytes(Z.device, nb)
+    call("fmx_gram_exact_rows", ptr(Z), ptr(rows), H, ptr(limbs), ptr(counts), F, D, A, A, int(d0), int(d1),
+         int(bool(accumulate)), ptr(work), wb, stream_ptr())
+    return limbs, counts
+
+
+def prune_head(limbs, counts, order, F, rho=0.7, top_x=5):
+    """The greedy prune from the (all-reduced) head block of gram_exact_rows(Z, order[:H])
+    (fmx_prune_head: finalize + walk in one launch, one host read).  Returns (kept factor
+    list, done); ``done``: the walk of the whole order over the full correlation matrix
+    returns the same list (top_x kept inside the head, or the head is the whole order) --
+    else ``kept`` is only its prefix."""
+    H = int(limbs.shape[1])
+    if tuple(limbs.shape) != (GRAM_EXACT_SLOTS, H, H) or limbs.dtype != torch.int64 or not limbs.is_contiguous() \
+            or tuple(counts.shape) != (H, H) or counts.dtype != torch.int64 or not counts.is_contiguous() \
+            or not 1 <= H <= GRAM_HEAD_MAX:
+        raise _lib.FmxError("prune_head: limbs int64 [7][H][H], counts int64 [H][H], H <= 64")
+    ordt = order.to(device=limbs.device, dtype=torch.int64).contiguous()
+    lim = max(int(top_x), 1)                        # as greedy_prune: top_x <= 0 keeps one
+    cap = min(lim, H)
+    out = torch.empty(cap + 2, dtype=torch.int32, device=limbs.device)     # kept | n_kept | done
+    call("fmx_prune_head", ptr(limbs), ptr(counts), ptr(ordt), H, int(ordt.numel()), int(F), float(rho), lim,
+         ptr(out), ptr(out[cap:]), ptr(out[cap + 1:]), stream_ptr())
+    res = out.cpu().tolist()
+    return [int(v) for v in res[:res[cap]]], bool(res[cap + 1])
+
+
+GRAM_CHUNK_BYTES = 8 << 30     # Z + M workspace of one date chunk of the wide Gram
 
 
 def gram_chunked(X, d0=0, d1=None, chunk=None):

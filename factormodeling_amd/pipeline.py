@@ -9,7 +9,9 @@ Step = the C2 hot path of BASELINE.json on a panel already resident in HBM:
      IC starts from those ranks (fmx_ic_daily_ranked) instead of ranking X again
   3. full-sample metrics + rolling W-window metrics for every processed day
   4. icir_top selection per day (top_x=5, threshold=-1, factor_selector.py:94-139)
-  5. correlation-based pruning: fp64-MFMA factor Gram + greedy prune (builder-defined)
+  5. correlation-based pruning: fp64-MFMA factor Gram + greedy prune (builder-defined);
+     with ``lazy_gram`` the Gram of the prune order's head block first, the full Gram only
+     when the walk leaves it
 
 Multi-GPU: ``ShardedPanel`` holds a rank's date shard plus a halo of the preceding
 dates; ``run_step`` exchanges the halo, runs 1-2 on local dates, all-gathers the daily
@@ -66,6 +68,9 @@ class StepConfig:
     # the whole step, next to the one-pass cross-sectional operators -> Gram -> IC chain on
     # the current stream (every operator output in its own buffer).  One shard only.
     overlap: bool = False
+    # prune from the Gram of the order's head block (lazy_gram_head); the full Gram only when
+    # the walk leaves the head.  FMX_LAZY_GRAM=0 turns the default off (A/B)
+    lazy_gram: bool = field(default_factory=lambda: os.environ.get("FMX_LAZY_GRAM", "1") != "0")
 
     @property
     def lookback(self):
@@ -139,6 +144,47 @@ def plan_ops(ops, be, fuse=True, zn=True):
         if all(p in left for p in pair):
             stages = [st for st in stages if st[1][0] not in pair] + [("cs_zscore_neutralize", pair)]
     return stages
+
+
+GRAM_HEADS = (16, 32, 48, 64)   # head sizes of the lazy Gram (whole 16-row MFMA blocks)
+
+
+def gram_head_size(top):
+    """Rows of the lazy Gram's head block for a prune that keeps ``top``: 32 (FMX_GRAM_HEAD
+    in GRAM_HEADS for A/B), and at least 2 * top rounded up to whole 16-row blocks."""
+    H = int(os.environ.get("FMX_GRAM_HEAD", "32"))
+    if H not in GRAM_HEADS:
+        raise ValueError(f"FMX_GRAM_HEAD must be one of {GRAM_HEADS}, got {H}")
+    return max(H, 16 * -(-2 * int(top) // 16))
+
+
+def lazy_gram_head(cfg, be, F, side, collect, top):
+    """Head size H when the step may prune from the Gram of order[:H] alone (the walk reads
+    only correlations among the candidates it visited, and stops at ``top`` kept), else 0:
+    the full Gram.  ``collect`` wants the whole C; a head of half the zoo or more saves too
+    little to pay for a fallback."""
+    if not (cfg.gram and cfg.lazy_gram) or cfg.streams or collect is not None:
+        return 0
+    if isinstance(top, bool) or not isinstance(top, (int, np.integer)) or top < 1:
+        return 0
+    if not (hasattr(be, "gram_exact_rows") and hasattr(be, "prune_head")) or F > E.FUSED_GRAM_MAX_F:
+        return 0
+    if side.get("zscore") is None:
+        return 0
+    H = gram_head_size(top)
+    return H if H <= GRAM_HEADS[-1] and 2 * H <= F else 0
+
+
+def _lazy_step_head(sp, cfg, be, side, collect, zn):
+    """lazy_gram_head for a step whose early stages have run: also, every stage still to run
+    must be the rolling set -- it overwrites the z-score buffer (sequential stages share the
+    buffers), so it is the one stage that moves behind the prune."""
+    top = cfg.top_x if cfg.prune_top_x == "top_x" else cfg.prune_top_x
+    H = lazy_gram_head(cfg, be, sp.F, side, collect, top)
+    if H and any(n not in EARLY_STAGES and not n.startswith("ts_set:")
+                 for n, _ in plan_ops(cfg.ops, be, cfg.fuse, zn=zn)):
+        return 0
+    return H
 
 
 def synthetic_panel(D, A, F, device, seed=0, d_lo=0, d_hi=None, halo=0):
@@ -373,6 +419,10 @@ class EngineBackend:
         return E.gram_exact(X, stats, d0, d1)
 
     gram_exact_finalize = staticmethod(E.gram_exact_finalize)
+    # the lazy Gram: exact partials of the rows a device index list names, and the prune
+    # from that head block
+    gram_exact_rows = staticmethod(E.gram_exact_rows)
+    prune_head = staticmethod(E.prune_head)
 
     @staticmethod
     def corr_gram_wide_exact(X, d0, d1, d_origin, stats=None):
@@ -646,6 +696,7 @@ def run_step(sp: ShardedPanel, cfg: StepConfig, timers=None, be=ENGINE, collect=
     halo = sp.exchange_halo_start()
     _rec(timers, "halo", t0)
     GN = None
+    lazy_H = 0
     if early:
         # while the halo is in flight: the stages whose owned-date results read no halo
         # row -- cs_zscore + market_neutralize (per-date rows) and the Gram over the owned
@@ -657,9 +708,13 @@ def run_step(sp: ShardedPanel, cfg: StepConfig, timers=None, be=ENGINE, collect=
                               own=slice(sp.halo, None), side=side, streams=[side_st] if overlap else None,
                               only=lambda n: n in early_names, zn=zn)
         if cfg.gram and hasattr(be, "corr_gram"):
-            t0 = _ev(timers)
-            GN = gram_partials(sp, be, side)
-            _rec(timers, "gram", t0)
+            # lazy: no Gram here -- the prune below computes the head block of its order, and
+            # the rolling set (which overwrites z) moves behind it
+            lazy_H = _lazy_step_head(sp, cfg, be, side, collect, zn)
+            if not lazy_H:
+                t0 = _ev(timers)
+                GN = gram_partials(sp, be, side)
+                _rec(timers, "gram", t0)
     t0 = _ev(timers)
     sp.exchange_halo_finish(halo)
     _rec(timers, "halo_wait", t0)
@@ -681,7 +736,7 @@ def run_step(sp: ShardedPanel, cfg: StepConfig, timers=None, be=ENGINE, collect=
             rest = lambda n: n not in early_names and not n.startswith("ts_set:")  # noqa: E731
             sp.bufs = run_ops(sp.X, cfg, getattr(sp, "bufs", None), timers=timers, be=be, collect=collect,
                               own=slice(sp.halo, None), side=side, streams=[side_st], only=rest, zn=zn)
-        else:
+        elif not lazy_H:                          # (lazy: only the rolling set is left; it runs after the prune)
             sp.bufs = run_ops(sp.X, cfg, getattr(sp, "bufs", None), timers=timers, be=be, collect=collect,
                               own=slice(sp.halo, None), side=side, streams=streams,
                               only=(lambda n: n not in early_names) if early else None, zn=zn)
@@ -760,7 +815,29 @@ def run_step(sp: ShardedPanel, cfg: StepConfig, timers=None, be=ENGINE, collect=
         for st in streams:
             main.wait_stream(st)
     kept = C = None
-    if cfg.gram:
+    if lazy_H:
+        # the prune from the head block of its order: the exact Gram of the z rows
+        # order[:H] over the owned dates (int64 all-reduce: every rank sees the same head and
+        # takes the same branch), finalize + walk in one launch, one host read
+        t0 = _ev(timers)
+        rir = summ[0, :, 3]
+        full_order = torch.argsort(torch.nan_to_num(rir, nan=-np.inf), descending=True, stable=True)
+        top = cfg.top_x if cfg.prune_top_x == "top_x" else cfg.prune_top_x
+        head = be.gram_exact_rows(side["zscore"], full_order[:lazy_H].contiguous(), sp.halo, sp.X.shape[1])
+        if sp.world > 1:
+            for T in head:
+                sp.comm.all_reduce_sum(T)
+        _rec(timers, "gram_head", t0)
+        t0 = _ev(timers)
+        kept, done = be.prune_head(head[0], head[1], full_order, sp.F, cfg.prune_rho, top)
+        _rec(timers, "prune", t0)
+        if not done:
+            # the walk left the head: the full Gram and prune, as without lazy_gram
+            kept = None
+            t0 = _ev(timers)
+            GN = gram_partials(sp, be, side)
+            _rec(timers, "gram", t0)
+    if cfg.gram and kept is None:
         # correlation Gram over owned dates, summed over ranks in rank order
         t0 = _ev(timers)
         made = GN is not None
@@ -779,6 +856,11 @@ def run_step(sp: ShardedPanel, cfg: StepConfig, timers=None, be=ENGINE, collect=
         top = cfg.top_x if cfg.prune_top_x == "top_x" else cfg.prune_top_x
         kept = be.greedy_prune(C, full_order.cpu().numpy(), cfg.prune_rho, top)
         _rec(timers, "prune", t0)
+    if lazy_H and cfg.ops and not overlap:
+        # the rolling set, held back while the prune read z (the stages share the buffers);
+        # it ends the step, so sp.bufs finish as they do without lazy_gram
+        sp.bufs = run_ops(sp.X, cfg, getattr(sp, "bufs", None), timers=timers, be=be, collect=collect,
+                          own=slice(sp.halo, None), side=side, only=lambda n: n not in early_names, zn=zn)
     if side_st is not None:                       # join the rolling set
         torch.cuda.current_stream(sp.X.device).wait_stream(side_st)
     if collect is not None:

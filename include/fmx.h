@@ -376,6 +376,26 @@ fmx_status fmx_gram_exact(const double* X, const double* stats, int64_t* limbs, 
                           int64_t D, int64_t A, int64_t ld, int64_t d0, int64_t d1, int32_t accumulate, void* work,
                           int64_t work_bytes, void* stream);
 int64_t fmx_gram_exact_work_bytes(int64_t F, int64_t D, int64_t A, int64_t d0, int64_t d1);
+/* fmx_gram_exact (z input only: X holds the z-scores) restricted to H <= 64 rows of the
+ * panel, named by the device list rows int64 [H] (never read by the host: no sync before
+ * the launch).  limbs [FMX_GRAM_EXACT_SLOTS][H][H] and counts [H][H] (upper triangles) are
+ * indexed by position in the list; an index outside [0, F) is an all-invalid row.  Same
+ * units, chunks and MFMA chain per unit as fmx_gram_exact, so every limb and count equals
+ * that entry's for the same factor pair bit for bit, at any d0, d1 and any date split.
+ * The panel rows are read in place (no gathered copy). */
+fmx_status fmx_gram_exact_rows(const double* Z, const int64_t* rows, int64_t H, int64_t* limbs, int64_t* counts,
+                               int64_t F, int64_t D, int64_t A, int64_t ld, int64_t d0, int64_t d1,
+                               int32_t accumulate, void* work, int64_t work_bytes, void* stream);
+int64_t fmx_gram_exact_rows_work_bytes(int64_t H, int64_t D, int64_t A, int64_t d0, int64_t d1);
+/* The step's prune from a head block: C = N > 0 ? G / N : 0 of the (all-reduced) limbs
+ * [FMX_GRAM_EXACT_SLOTS][H][H] / counts [H][H] of fmx_gram_exact_rows(order[0..H)), then
+ * fmx_greedy_prune's walk over positions 0 .. min(H, n_order) - 1 (order entries outside
+ * [0, F) are skipped), in one workgroup.  kept (int32 [min(top_x, H)], factor indices),
+ * n_kept and done (int32 [1] each) are device buffers; done = n_kept == top_x or
+ * H >= n_order: the walk of the whole order would return the same list.  H <= 64. */
+fmx_status fmx_prune_head(const int64_t* limbs, const int64_t* counts, const int64_t* order, int64_t H,
+                          int64_t n_order, int64_t F, double rho, int64_t top_x, int32_t* kept, int32_t* n_kept,
+                          int32_t* done, void* stream);
 /* Exact, GPU-count-independent form of fmx_gram_direct (any F; C4's 2000 x 2000 at
  * 2/4/8 GPUs, builder-defined A19).  The tile kernel's date slices are ABSOLUTE blocks of
  * FMX_GRAM_DATE_BLOCK dates (local row 0 of X is absolute date d_origin); each block's fp64

@@ -89,8 +89,23 @@ def _pres(X):
     return _PR["p"]
 
 
+_HR = {}
+
+
+def _head_rows_n(F):
+    return min(int(os.environ.get("KB_GRAM_HEAD", "32")), F)
+
+
+def _head_rows(X):
+    """a device list of distinct rows in no order (made once): the head of a prune order."""
+    if "r" not in _HR:
+        g = torch.Generator(device="cpu").manual_seed(7)
+        _HR["r"] = torch.randperm(X.shape[0], generator=g)[:_head_rows_n(X.shape[0])].to(X.device)
+    return _HR["r"]
+
+
 OPS = {
-    "ts_mean": (lambda X, R, Y: E.ts("mean", X, 20, out=Y), 16),
+    "ts_mean":(lambda X, R, Y: E.ts("mean", X, 20, out=Y), 16),
     "ts_std": (lambda X, R, Y: E.ts("std", X, 20, out=Y), 16),
     "ts_zscore": (lambda X, R, Y: E.ts("zscore", X, 20, out=Y), 16),
     "ts_rank": (lambda X, R, Y: E.ts("rank", X, 10, out=Y), 16),
@@ -130,6 +145,9 @@ OPS = {
     "gram": (lambda X, R, Y: E.corr_matrix(X), 8),
     # the C2 step's Gram: exact fixed-point partials from the cs_zscore output (Y after cs_zn)
     "gram_exact_z": (lambda X, R, Y: E.gram_exact(Y, None), 8),
+    # the lazy step's head block: the exact Gram of KB_GRAM_HEAD (32) scattered rows of Y, read in
+    # place (bytes: those rows only)
+    "gram_rows": (lambda X, R, Y: E.gram_exact_rows(Y, _head_rows(X)), lambda F: 8.0 * _head_rows_n(F) / F),
     # the C4 step's Gram straight from the panel (row stats + validity bits + tiles + popcount)
     "gram_direct": (lambda X, R, Y: E.gram_direct(X), 8),
     # the C4 step's exact Gram (absolute 16-date blocks folded into fixed-point limbs)
@@ -344,6 +362,8 @@ def main():
     res = {}
     for name in a.ops.split(","):
         fn, bpu = OPS[name]
+        if callable(bpu):
+            bpu = bpu(F)
         fn(X, R, Y)
         torch.cuda.synchronize()
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
