@@ -408,6 +408,44 @@ def cs_regression(Yv, Xv, rettype: str, present=None):
     return out
 
 
+CS_OLS_MAX_K = 32           # fmx_cs_ols: the factor is a 33 x 33 matrix in LDS
+CS_OLS_MAX_A = 16384        # the row kernels' cap (uint16 positions)
+CS_OLS_OUTPUTS = ("beta", "alpha", "r2", "n", "resid", "fitted")
+
+
+def cs_ols(Y, X, W=None, present=None, intercept=True, want=CS_OLS_OUTPUTS):
+    """Per-date multi-factor OLS (fmx_cs_ols): every column of ``Y`` [Fy][D][A]
+    (or [D][A]) regressed per date on the K columns of ``X`` [K][D][A] over the valid rows,
+    optionally weighted by ``W`` [D][A].  Returns a dict of device tensors for the names in
+    ``want``: beta [Fy][D][K], alpha / r2 [Fy][D], n [Fy][D] int32, resid / fitted
+    [Fy][D][A].  Collinear columns are dropped in column order (beta NaN)."""
+    Y = as3(Y)
+    _check_panel(Y, "Y")
+    _check_panel(X, "X")
+    Fy, D, A = Y.shape
+    K = X.shape[0]
+    if tuple(X.shape[1:]) != (D, A):
+        raise _lib.FmxError(f"cs_ols: X is {tuple(X.shape)}, expected [K][{D}][{A}] to match Y")
+    if W is not None:
+        if (not isinstance(W, torch.Tensor) or W.device.type != "cuda" or W.dtype != F64
+                or tuple(W.shape) != (D, A) or not W.is_contiguous()):
+            raise _lib.FmxError(f"cs_ols: W must be a contiguous float64 [{D}][{A}] device tensor")
+    _check_present(present, D, A)
+    if not 1 <= K <= CS_OLS_MAX_K:
+        raise _lib.FmxError(f"cs_ols: K = {K} regressors; the kernel takes 1..{CS_OLS_MAX_K}")
+    if A > CS_OLS_MAX_A:
+        raise _lib.FmxError(f"cs_ols: A = {A} assets; the kernel takes rows up to {CS_OLS_MAX_A}")
+    bad = set(want) - set(CS_OLS_OUTPUTS)
+    if bad:
+        raise ValueError(f"cs_ols: unknown outputs {sorted(bad)}")
+    dev = Y.device
+    shapes = dict(beta=(Fy, D, K), alpha=(Fy, D), r2=(Fy, D), n=(Fy, D), resid=(Fy, D, A), fitted=(Fy, D, A))
+    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "n" else F64, device=dev) for k in want}
+    call("fmx_cs_ols", ptr(Y), ptr(X), ptr(W), ptr(present), Fy, K, D, A, A, int(bool(intercept)),
+         *(ptr(out.get(k)) for k in CS_OLS_OUTPUTS), stream_ptr())
+    return out
+
+
 def elementwise(op: str, X, a=0.0, b=0.0):
     X = X.contiguous()
     Y = torch.empty_like(X)

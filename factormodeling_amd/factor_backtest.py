@@ -276,3 +276,31 @@ def single_factor_returns(factors_df: pd.DataFrame, settings, columns=None, fiel
     if field not in _ps().RESULT_COLS + COUNT_COLS:
         raise ValueError(f"field must be one of {_ps().RESULT_COLS + COUNT_COLS}, got {field!r}")
     return single_factor_backtests(factors_df, settings, columns=columns, **kw)[field]
+
+
+def cross_sectional_factor_returns(factors_df: pd.DataFrame, returns: pd.Series, lag: int = 1,
+                                   intercept: bool = True, weights=None, full: bool = False):
+    """Pure factor returns (Fama-MacBeth / Barra style; builder-defined): on every date the
+    returns are regressed on ALL factor columns at once, each shifted ``lag`` rows per symbol
+    (``ts_delay``, row-based on ragged panels), by ``engine.cs_ols``.  ``returns`` and
+    ``weights`` are aligned to ``factors_df.index``.  Returns the ``dates x factors`` table of
+    coefficients (index named ``date``, columns in input order; a collinear column's return is
+    NaN on that date, and so is every column of a date with fewer rows than coefficients) --
+    usable as ``FactorSelector``'s ``factor_ret_df``.  ``full=True`` returns
+    ``(table, stats)`` with ``stats`` a DataFrame of ``alpha``, ``r2`` and ``n`` per date."""
+    pi = panel_index(factors_df.index)
+    dev = device()
+    present = pi.present(dev)
+    X = E.ts("delay", pi.to_device(factors_df.to_numpy(dtype=np.float64, na_value=np.nan), dev), int(lag), present)
+    Y = pi.to_device(returns.reindex(factors_df.index).to_numpy(dtype=np.float64, na_value=np.nan), dev)
+    W = None
+    if weights is not None:
+        W = pi.to_device(weights.reindex(factors_df.index).to_numpy(dtype=np.float64, na_value=np.nan), dev)[0]
+    res = E.cs_ols(Y, X, W, present, intercept, want=("beta", "alpha", "r2", "n") if full else ("beta",))
+    dates = pd.Index(pi.dates, name="date")
+    table = pd.DataFrame(res["beta"][0].cpu().numpy(), index=dates, columns=factors_df.columns)
+    if not full:
+        return table
+    stats = pd.DataFrame({"alpha": res["alpha"][0].cpu().numpy(), "r2": res["r2"][0].cpu().numpy(),
+                          "n": res["n"][0].cpu().numpy()}, index=dates)
+    return table, stats

@@ -25,6 +25,7 @@ __all__ = [
     "ts_corr", "cs_rank", "cs_winsor", "cs_filter_center", "cs_zscore", "cs_bool", "cs_mean", "sign", "power",
     "log", "abs_", "clip", "bucket", "group_mean", "group_neutralize", "group_normalize",
     "group_rank_normalized", "market_neutralize", "ts_regression_fast", "cs_regression",
+    "cs_regression_multi",
 ]
 
 
@@ -284,3 +285,43 @@ def cs_regression(y, x, rettype: str = "resid"):
     Xd = P.to_device(xv, dev)[0]
     out = engine.cs_regression(Yd, Xd, rettype, P.present(dev))
     return pd.Series(P.from_device(out[None])[:, 0], index=y.index)
+
+
+def cs_regression_multi(y, X, rettype: str = "resid", intercept: bool = True, weights=None):
+    """Builder-defined (no reference counterpart): per-date least squares of ``y`` on the K
+    columns of the DataFrame ``X`` (``engine.cs_ols``), optionally weighted and with an
+    intercept; ``X`` and ``weights`` are aligned to ``y``'s index.  ``y`` is a Series or a
+    DataFrame of columns (one batched call).  A row enters a date's fit when y, every X column
+    and the weight (> 0) are finite; columns collinear with the ones before them are dropped.
+
+    ``rettype`` in resid | fitted | alpha | r2 returns an object like ``y`` (alpha and r2
+    broadcast over the fitted rows, NaN elsewhere); ``"beta"`` returns a ``dates x X.columns``
+    DataFrame and needs a Series ``y``."""
+    if rettype not in ("resid", "fitted", "alpha", "r2", "beta"):
+        raise ValueError(f"ERROR: rettype={rettype}")
+    if not isinstance(X, pd.DataFrame):
+        raise ValueError("X must be a DataFrame of regressor columns")
+    frame = isinstance(y, pd.DataFrame)
+    if rettype == "beta" and frame:
+        raise ValueError("rettype='beta' needs a Series y (one coefficient table per y column)")
+    P = panel_index(y.index)
+    dev = device()
+    Yd = P.to_device(_matrix(y), dev)
+    Xd = P.to_device(X.reindex(y.index).to_numpy(dtype=np.float64, na_value=np.nan), dev)
+    Wd = None
+    if weights is not None:
+        Wd = P.to_device(weights.reindex(y.index).to_numpy(dtype=np.float64, na_value=np.nan), dev)[0]
+    present = P.present(dev)
+    if rettype == "beta":
+        beta = engine.cs_ols(Yd, Xd, Wd, present, intercept, want=("beta",))["beta"][0]
+        return pd.DataFrame(beta.cpu().numpy(), index=pd.Index(P.dates, name="date"), columns=X.columns)
+    if rettype in ("resid", "fitted"):
+        out = engine.cs_ols(Yd, Xd, Wd, present, intercept, want=(rettype,))[rettype]
+    else:
+        # the per-date scalar on the rows of the fit: resid is non-NaN exactly there
+        res = engine.cs_ols(Yd, Xd, Wd, present, intercept, want=(rettype, "resid"))
+        out = torch.where(torch.isnan(res["resid"]), res["resid"], res[rettype].unsqueeze(-1))
+    vals = P.from_device(out)
+    if frame:
+        return pd.DataFrame(vals, index=y.index, columns=y.columns)
+    return pd.Series(vals[:, 0], index=y.index, name=y.name)

@@ -651,6 +651,26 @@ fmx_status fmx_qbucket_mean(const uint8_t* labels, const double* R, const uint8_
                             double* mean, int32_t* count, int64_t F, int64_t D, int64_t A, int32_t n_groups,
                             void* stream);
 
+/* ---- per-date multi-factor OLS (builder-defined) ---------------------- */
+/* For every (y column f, date d): weighted least squares of Y[f][d][:] on the K columns
+ * X[:][d][:] over the VALID rows -- present, Y finite, all K X finite and, with W, W finite
+ * and > 0.  n = #valid rows, p = K + intercept; n < p makes every output of (f, d) NaN but n.
+ * With an intercept the columns are centred on their weighted means; G = Xc' W Xc is scaled
+ * to unit diagonal by s_k = sqrt(G_kk) and factored by a Cholesky in column order.  Column k
+ * is DROPPED (beta NaN, no contribution to fitted) when s_k == 0, when (intercept only)
+ * s_k <= 1e-13 sqrt(sum w x_k^2), or when its pivot after eliminating the kept columns
+ * before it is < 1e-10.  alpha = ybar - sum_kept beta_k xbar_k (NaN without an intercept);
+ * r2 = 1 - SSR / SST, both weighted, SST centred iff intercept, NaN if SST == 0.
+ *   Y [Fy][D][ld], X [K][D][ld], W [D][ld] or NULL, present [D][ld] or NULL;
+ *   beta [Fy][D][K], alpha / r2 [Fy][D], n [Fy][D] int32, resid / fitted [Fy][D][ld] (NaN
+ *   on rows that are not valid).  Any output pointer may be NULL.
+ * Sums run in a fixed order that depends on (K, n) only: a column's bits do not depend on
+ * the other columns of the batch, nor on the run.  1 <= K <= 32 and A <= 16384; anything
+ * else is FMX_ERR_ARG before any launch. */
+fmx_status fmx_cs_ols(const double* Y, const double* X, const double* W, const uint8_t* present, int64_t Fy,
+                      int64_t K, int64_t D, int64_t A, int64_t ld, int32_t intercept, double* beta, double* alpha,
+                      double* r2, int32_t* n, double* resid, double* fitted, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
