@@ -44,6 +44,11 @@ __device__ __forceinline__ int fr_opaque(int v) {
   asm volatile("" : "+v"(v));
   return v;
 }
+// The same for a block-uniform word held in a scalar register.
+__device__ __forceinline__ uint32_t fr_opaque_s(uint32_t v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
 __device__ __forceinline__ int fr_xor_i(int v, int m, int lane) {
   return __builtin_amdgcn_ds_bpermute((lane ^ m) << 2, v);
 }

@@ -76,13 +76,27 @@ constexpr uint64_t KEY_SENTINEL = 0xffffffffffffffffull;  // sorts after +inf
 // fma rounding returns exactly the IEEE quotient (Markstein's correction).  3 fp64 ops in place
 // of the ~10-instruction v_div_scale / v_rcp / Newton / v_div_fixup sequence.  Zero, tiny,
 // huge and non-finite quotients take the IEEE divide (sign of zero, no under/overflow).
-// The range guard reads q0's biased exponent with full-rate integer ops (fp64 compares
-// issue at the quarter fp64 rate): exponents outside [64, 1958] (|q0| < 2^-959 incl. zero,
-// |q0| >= 2^936, inf, NaN) take the divide.
+// The range guard reads q0's biased exponent with integer ops: exponents outside [64, 1958]
+// (|q0| < 2^-959 incl. zero, |q0| >= 2^936, inf, NaN) take the divide.  (An integer VALU
+// instruction holds its SIMD for about as long as an fp64 add, ~4 cycles per wave64
+// instruction by the SQ counters, DESIGN section 5: the guard costs its three instructions,
+// it is not free.)
 __device__ __forceinline__ double mdiv(double x, double n, double r) {
   const double q0 = x * r;
   const uint32_t e = ((uint32_t)__double2hiint(q0) >> 20) & 0x7ffu;
   if (e - 64u > 1958u - 64u) return x / n;
+  const double rem = __builtin_fma(-q0, n, x);
+  return __builtin_fma(rem, r, q0);
+}
+// mdiv for an integer numerator 0 <= k < 2^31 over a divisor 1 <= n < 2^31 (the rank outputs:
+// k = 2 #less + #equal - 1 <= 2 A, n = 2 (len - 1)): q0 = RN(k r) lies in [2^-32, 2^32] for
+// every k >= 1, far inside mdiv's exponent window, so the guard is false exactly when k = 0
+// and is tested on the integer, before the conversion; k = 0 still takes the IEEE divide.
+// tests/native/mdiv_rank_check.c: bit-identical to (double)k / n on the host.
+__device__ __forceinline__ double mdiv_rank(int k, double n, double r) {
+  const double x = (double)k;
+  if (k == 0) return x / n;
+  const double q0 = x * r;
   const double rem = __builtin_fma(-q0, n, x);
   return __builtin_fma(rem, r, q0);
 }

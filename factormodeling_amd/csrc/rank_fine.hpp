@@ -36,12 +36,54 @@ constexpr int fr_fa_min_waves(int nt, int emax) {
 // next instantiated EMAX (7 -> 8, 9 -> 10, 11 -> 12, 13..15 -> 16, ...), so any slot, not
 // just the last, may lie past the row's end: every slot is tested, and the unconditional
 // loads are clamped into the row.
-template <int NT>
-__device__ __forceinline__ bool fr_in(int t, int k, int A) { return t + k * NT < A; }
+// The slots that can do so are known at compile time: br_emax takes the SMALLEST instantiated
+// EMAX >= ceil(A / NT), so ceil(A / NT) exceeds the table entry before EMAX and every slot
+// k < fr_emax_prev(EMAX) lies wholly inside the row (t + k*NT < fr_emax_prev * NT < A).
+// The fused four-operator pass (k_cs_rank_fa<..., ZN>) tests and clamps only the slots from
+// there on (<512, 10>: slots 8 and 9): fr_in<NT, EMAX>.
+// fr_emax_prev reads the launcher's own table (BR_EMAX_TAB, rank_kernels.hpp): an EMAX that
+// is not in it has no guaranteed slot.
+constexpr int fr_emax_prev(int emax) {
+  int prev = 0;
+  for (int v : BR_EMAX_TAB) {
+    if (v == emax) return prev;
+    prev = v;
+  }
+  return 0;
+}
+// EMAX = 0 (the default): the run-time test of every slot.
+template <int NT, int EMAX = 0>
+__device__ __forceinline__ bool fr_in(int t, int k, int A) {
+  if constexpr (EMAX == 0) {
+    return t + k * NT < A;
+  } else {
+    constexpr int P = fr_emax_prev(EMAX);
+    return k < P || t + k * NT < A;
+  }
+}
 template <int NT>
 __device__ __forceinline__ int fr_ix(int t, int k, int A) {
   const int i = t + k * NT;
   return i < A ? i : (A > 0 ? A - 1 : 0);
+}
+// Row element addressing of k_cs_rank_fa: a block-uniform row base (scalar registers) plus
+// one 32-bit byte offset per lane, ob = 8 t, advanced by the constant 8 k NT per slot -- the
+// four fp64 outputs share it and the 16-bit ranks take a quarter of it (A <= 65535: the
+// offsets stay far below 2^32).  Loads clamp the offset of the slots that may leave the row.
+template <class T>
+__device__ __forceinline__ T* fr_at(T* base, uint32_t boff) {
+  return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + boff);
+}
+template <class T>
+__device__ __forceinline__ const T* fr_at(const T* base, uint32_t boff) {
+  return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + boff);
+}
+template <int NT, int EMAX>
+__device__ __forceinline__ uint32_t fr_ldoff(uint32_t ob, int k, int A) {
+  constexpr int P = fr_emax_prev(EMAX);
+  const uint32_t o = ob + (uint32_t)(k * NT * 8);
+  if (k < P) return o;
+  return min(o, (uint32_t)(A > 0 ? A - 1 : 0) * 8u);
 }
 // Scheduling fence between unrolled per-element steps: bounds how many elements' live
 // ranges overlap (register pressure at 8 waves/SIMD) -- other waves hide the latency.
@@ -345,7 +387,9 @@ __device__ __forceinline__ void fr_ic_tail(const FrIc& ic, const FrIcRow& rw, in
 // latency chain), so the bucket counters and the bucketed keys share one buffer: the
 // counters are read into registers after their scan, and only then are the keys of
 // shared fine buckets scattered over them.  ~42 KB per row: three rows per CU.
-// Positions t + k*NT with k < EMAX-1 are always inside the row (EMAX = ceil(A/NT)).
+// Positions t + k*NT with k < fr_emax_prev(EMAX) are always inside the row; EMAX is
+// ceil(A/NT) rounded up to an instantiated count, so the later slots -- more than one where
+// the table skips a count (9 -> 10: slots 8 and 9) -- may lie past its end.
 //
 // WQ: also cs_winsor of the same row into Y2 (operations.py:64-68) from the same histogram.
 // The four numpy 'linear' order statistics are read off the ranks: after the in-bucket
@@ -375,6 +419,17 @@ k_cs_rank_fa(const double* __restrict__ X, double* __restrict__ Y, int64_t D, in
   constexpr int K = FR_K_CS, NW = NT / 64;
   constexpr int WORDS = FR_CS_WORDS, DUMMY = 2 * WORDS - 1;   // sentinel bucket: last half-word
   static_assert(FRG<K>::NB + 1 < DUMMY, "counter array");
+  // The per-element bookkeeping diet (compile-time slot tests, scalar row bases with one lane
+  // offset, the paired winsor owner test, the scalar switch word, the integer division guard)
+  // is taken by the fused four-operator pass, in the instantiations a launcher can select
+  // (br_emax: EMAX * NT <= 16384).  The other instantiations sit at their VGPR caps and the
+  // register allocator answers these edits with more scratch in a dozen of them
+  // (profiles/fused_diet/resource_usage_whole_template.txt), so they keep the parent's
+  // statements, in blocks of their own: the slot tests, the loads, the output loop and the
+  // winsor clip each exist once per arm.
+  constexpr bool DIET = ZN && EMAX * NT <= 16384;
+  constexpr int EP = DIET ? EMAX : 0;
+  static_assert(!DIET || (!PRES && !IC), "the diet's stores assume dense rows without the fused IC");
   __shared__ FrTab tab;
   __shared__ uint4 wred[NW];                  // per wave: #present, #valid, min / max key high words
   __shared__ int iscr[NW];
@@ -411,18 +466,24 @@ k_cs_rank_fa(const double* __restrict__ X, double* __restrict__ Y, int64_t D, in
   int wv = 0, wp = 0;                         // wave-uniform counts (ballots)
   // every load of the row issued before the first is consumed: a load under a branch (the
   // key conversion below is one per element) waits out the previous one's HBM latency.
-  // The last slot is clamped into the row (its value is unused when out of range).
+  // The slots that may leave the row are clamped into it (their value is unused out of range).
   double xv[EMAX];
   uint32_t pv = 0;
+  if constexpr (DIET) {
+    const uint32_t ob = (uint32_t)fr_opaque(t) * 8u;
 #pragma unroll
-  for (int k = 0; k < EMAX; ++k) xv[k] = x[fr_ix<NT>(fr_opaque(t), k, (int)A)];
+    for (int k = 0; k < EMAX; ++k) xv[k] = *fr_at(x, fr_ldoff<NT, EMAX>(ob, k, (int)A));
+  } else {
+#pragma unroll
+    for (int k = 0; k < EMAX; ++k) xv[k] = x[fr_ix<NT>(fr_opaque(t), k, (int)A)];
+  }
   if (PRES) {
 #pragma unroll
     for (int k = 0; k < EMAX; ++k) pv |= (prow[fr_ix<NT>(t, k, (int)A)] != 0 ? 1u : 0u) << k;
   }
 #pragma unroll
   for (int k = 0; k < EMAX; ++k) {
-    const bool in = fr_in<NT>(t, k, (int)A);
+    const bool in = fr_in<NT, EP>(t, k, (int)A);
     const double v = xv[k];
     const bool p = in && (PRES ? ((pv >> k) & 1u) != 0 : true);
     const bool ok = p && v == v;
@@ -434,7 +495,7 @@ k_cs_rank_fa(const double* __restrict__ X, double* __restrict__ Y, int64_t D, in
     wv += __popcll(__ballot(ok));
     if (PRES) wp += __popcll(__ballot(p));
     if constexpr (ZN)
-      if (in) reinterpret_cast<double*>(lds)[fr_opaque(t) + k * NT] = v;   // the row for the moments
+      if (in) reinterpret_cast<double*>(lds)[(DIET ? t : fr_opaque(t)) + k * NT] = v;   // the row for the moments
   }
   BR_PH();
   if constexpr (ZN) {
@@ -502,13 +563,28 @@ k_cs_rank_fa(const double* __restrict__ X, double* __restrict__ Y, int64_t D, in
     const bool sd_ok = rdiv_ok(sd);
     double* yz = zn.Yz + row * ld;
     double* yn = zn.Yn + row * ld;
+    if constexpr (DIET) {
+      // one lane offset for the staged row (the slot's 8 k NT is the LDS read's immediate) and
+      // both outputs, formed here and dead after the loop
+      const uint32_t ob = (uint32_t)fr_opaque(t) * 8u;
+      const double* vlane = fr_at(vrow, ob);
 #pragma unroll
-    for (int k = 0; k < EMAX; ++k) {
-      if (!fr_in<NT>(t, k, (int)A)) continue;
-      const int ia = fr_opaque(t) + k * NT;
-      const double o = rdiv(vrow[ia] - mean, sd, rsd, sd_ok);
-      __builtin_nontemporal_store(o, yz + ia);
-      __builtin_nontemporal_store(g2 ? 0.0 : o, yn + ia);
+      for (int k = 0; k < EMAX; ++k) {
+        if (!fr_in<NT, EMAX>(t, k, (int)A)) continue;
+        const uint32_t oa = ob + (uint32_t)(k * NT * 8);
+        const double o = rdiv(vlane[k * NT] - mean, sd, rsd, sd_ok);
+        __builtin_nontemporal_store(o, fr_at(yz, oa));
+        __builtin_nontemporal_store(g2 ? 0.0 : o, fr_at(yn, oa));
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < EMAX; ++k) {
+        if (!fr_in<NT>(t, k, (int)A)) continue;
+        const int ia = fr_opaque(t) + k * NT;
+        const double o = rdiv(vrow[ia] - mean, sd, rsd, sd_ok);
+        __builtin_nontemporal_store(o, yz + ia);
+        __builtin_nontemporal_store(g2 ? 0.0 : o, yn + ia);
+      }
     }
     __syncthreads();                          // every read of the staged row is done
     BR_PH();
@@ -540,17 +616,17 @@ k_cs_rank_fa(const double* __restrict__ X, double* __restrict__ Y, int64_t D, in
     if (Y) {                                  // Y == NULL: doubled ranks only (fmx_cs_rank2)
 #pragma unroll
       for (int k = 0; k < EMAX; ++k)
-        if (fr_in<NT>(t, k, (int)A)) y[fr_opaque(t) + k * NT] = (((pm >> k) & 1) && half) ? 0.5 : qnan();
+        if (fr_in<NT, EP>(t, k, (int)A)) y[fr_opaque(t) + k * NT] = (((pm >> k) & 1) && half) ? 0.5 : qnan();
     }
     if (RK) {                                 // nv == 0 or a single-row date (rank 1)
 #pragma unroll
       for (int k = 0; k < EMAX; ++k)
-        if (fr_in<NT>(t, k, (int)A)) RK[row * ld + fr_opaque(t) + k * NT] = (fmx_rank2_t)(key[k] == KEY_SENTINEL ? 0u : 2u);
+        if (fr_in<NT, EP>(t, k, (int)A)) RK[row * ld + fr_opaque(t) + k * NT] = (fmx_rank2_t)(key[k] == KEY_SENTINEL ? 0u : 2u);
     }
     if (WQ) {                                 // nv < 5: winsor is the identity
 #pragma unroll
       for (int k = 0; k < EMAX; ++k)
-        if (fr_in<NT>(t, k, (int)A)) Y2[row * ld + fr_opaque(t) + k * NT] = key[k] == KEY_SENTINEL ? qnan() : okey_inv(key[k]);
+        if (fr_in<NT, EP>(t, k, (int)A)) Y2[row * ld + fr_opaque(t) + k * NT] = key[k] == KEY_SENTINEL ? qnan() : okey_inv(key[k]);
     }
     if constexpr (IC) {                       // < 3 pairs: empty records (n = 0, or 1 on a one-asset row)
       if (t == 0) {
@@ -688,41 +764,88 @@ k_cs_rank_fa(const double* __restrict__ X, double* __restrict__ Y, int64_t D, in
   }
   uint32_t r2[IC ? (EMAX + 1) / 2 : 1];       // IC: doubled ranks (0: NaN), two 16-bit per word
   uint32_t em = 0;                            // IC: bit 2k+m = non-NaN exposure, NaN lag-m return
+  if constexpr (DIET) {
+    // The fused pass's output loop addresses from scalar row bases and one lane offset (fr_at),
+    // and tests its block-uniform switches as bits of one scalar word: kept as booleans the
+    // switches live as 64-bit lane masks, which the unrolled loop re-derives per element through
+    // a VGPR (v_cndmask + v_cmp) or parks in VGPR lanes.  The word is re-read as an unknown
+    // scalar at each test (fr_opaque_s), or the compiler turns the tests back into hoisted masks.
+    enum : uint32_t { U_WQ = 1u, U_RK = 2u };
+    fmx_rank2_t* rkrow = RK ? RK + row * ld : nullptr;
+    const uint32_t usw = (uint32_t)__builtin_amdgcn_readfirstlane((int)((nv >= 5 ? U_WQ : 0u) | (RK ? U_RK : 0u)));
+    auto sw = [&](uint32_t bit) { return (fr_opaque_s(usw) & bit) != 0u; };
+    const uint32_t ob = (uint32_t)fr_opaque(t) * 8u;   // formed here, not kept from the loads
 #pragma unroll
-  for (int k = 0; k < EMAX; ++k) {
-    if constexpr (IC) if (k % 2 == 0) r2[k / 2] = 0u;
-    if (!fr_in<NT>(t, k, (int)A)) continue;
-    const int lt = le[k] & 0xffff, eq = le[k] >> 16;
-    const int less = (sl[k] & 0xffff) + lt;
-    if constexpr (IC) r2[k / 2] |= (key[k] != KEY_SENTINEL ? (uint32_t)(2 * less + eq + 1) : 0u) << (16 * (k % 2));
-    // write-once outputs: nontemporal stores
-    const int ia = fr_opaque(t) + k * NT;       // recomputed here, not kept from the loads
-    if constexpr (ZN) {
+    for (int k = 0; k < EMAX; ++k) {
+      if (!fr_in<NT, EMAX>(t, k, (int)A)) continue;
+      const int lt = le[k] & 0xffff, eq = le[k] >> 16;
+      const int less = (sl[k] & 0xffff) + lt;
+      // write-once outputs: nontemporal stores
+      const uint32_t oa = ob + (uint32_t)(k * NT * 8);
       // method average: (r - 1) / den with r = r2 / 2, r2 = 2 less + eq + 1 the doubled rank;
       // (r2 - 2) / (2 den) is the same real number (r - 1 = (r2 - 2) / 2 exactly), so
-      // mdiv(r2 - 2, 2 den, RN(1 / den) / 2) gives the same bits from one conversion
-      const double q = mdiv((double)(2 * less + eq - 1), 2.0 * den, 0.5 * rden);
-      __builtin_nontemporal_store(key[k] == KEY_SENTINEL ? qnan() : q, y + ia);
-    } else {
-      double r;
-      if (method == FMX_RANK_MIN) r = (double)(less + 1);
-      else if (method == FMX_RANK_MAX) r = (double)(less + eq);
-      else r = (double)less + (double)(eq + 1) / 2.0;
-      if (Y) __builtin_nontemporal_store(key[k] == KEY_SENTINEL ? qnan() : mdiv(r - 1.0, den, rden), y + ia);
-    }
-    if (RK) __builtin_nontemporal_store((fmx_rank2_t)(key[k] == KEY_SENTINEL ? 0u : (uint32_t)(2 * less + eq + 1)),
-                                        RK + row * ld + ia);
-    if (WQ && nv >= 5) {
+      // mdiv(r2 - 2, 2 den, RN(1 / den) / 2) gives the same bits from one conversion; the
+      // numerator is an integer, so mdiv's range guard is a test of it (mdiv_rank)
+      const double q = mdiv_rank(2 * less + eq - 1, 2.0 * den, 0.5 * rden);
+      __builtin_nontemporal_store(key[k] == KEY_SENTINEL ? qnan() : q, fr_at(y, oa));
+      if (sw(U_RK))
+        __builtin_nontemporal_store((fmx_rank2_t)(key[k] == KEY_SENTINEL ? 0u : (uint32_t)(2 * less + eq + 1)),
+                                    fr_at(rkrow, oa >> 2));
       // the owners of the four order statistics (less <= kk < less + eq) publish their key;
-      // four hits per row, so the divergent stores sit behind a wave-uniform test
-      uint32_t hm = 0;
+      // four hits per row, so the divergent stores sit behind a wave-uniform test.  The four
+      // are two adjacent pairs (kk[2z + 1] - kk[2z] is 0 or 1), and owning either of pair z
+      // implies 0 <= kk[2z + 1] - less <= eq: one test per pair feeds the ballot, the exact
+      // four run inside the branch.  A sentinel key has less = nv > kk[j]: it never passes.
+      if (sw(U_WQ)) {
+        const bool cand = (uint32_t)(kk[1] - less) <= (uint32_t)eq || (uint32_t)(kk[3] - less) <= (uint32_t)eq;
+        if (__builtin_amdgcn_ballot_w64(cand)) {
+          uint32_t hm = 0;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) hm |= ((uint32_t)(kk[j] - less) < (uint32_t)eq ? 1u : 0u) << j;
-      if (key[k] == KEY_SENTINEL) hm = 0;
-      if (__builtin_amdgcn_ballot_w64(hm != 0)) {
+          for (int j = 0; j < 4; ++j) hm |= ((uint32_t)(kk[j] - less) < (uint32_t)eq ? 1u : 0u) << j;
+          if (key[k] == KEY_SENTINEL) hm = 0;
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if ((hm >> j) & 1u) tval[j] = key[k];   // all writers store the same key
+          for (int j = 0; j < 4; ++j)
+            if ((hm >> j) & 1u) tval[j] = key[k];   // all writers store the same key
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < EMAX; ++k) {
+      if constexpr (IC) if (k % 2 == 0) r2[k / 2] = 0u;
+      if (!fr_in<NT>(t, k, (int)A)) continue;
+      const int lt = le[k] & 0xffff, eq = le[k] >> 16;
+      const int less = (sl[k] & 0xffff) + lt;
+      if constexpr (IC) r2[k / 2] |= (key[k] != KEY_SENTINEL ? (uint32_t)(2 * less + eq + 1) : 0u) << (16 * (k % 2));
+      // write-once outputs: nontemporal stores
+      const int ia = fr_opaque(t) + k * NT;       // recomputed here, not kept from the loads
+      if constexpr (ZN) {
+        // method average: (r - 1) / den with r = r2 / 2, r2 = 2 less + eq + 1 the doubled rank;
+        // (r2 - 2) / (2 den) is the same real number (r - 1 = (r2 - 2) / 2 exactly), so
+        // mdiv(r2 - 2, 2 den, RN(1 / den) / 2) gives the same bits from one conversion
+        const double q = mdiv((double)(2 * less + eq - 1), 2.0 * den, 0.5 * rden);
+        __builtin_nontemporal_store(key[k] == KEY_SENTINEL ? qnan() : q, y + ia);
+      } else {
+        double r;
+        if (method == FMX_RANK_MIN) r = (double)(less + 1);
+        else if (method == FMX_RANK_MAX) r = (double)(less + eq);
+        else r = (double)less + (double)(eq + 1) / 2.0;
+        if (Y) __builtin_nontemporal_store(key[k] == KEY_SENTINEL ? qnan() : mdiv(r - 1.0, den, rden), y + ia);
+      }
+      if (RK) __builtin_nontemporal_store((fmx_rank2_t)(key[k] == KEY_SENTINEL ? 0u : (uint32_t)(2 * less + eq + 1)),
+                                          RK + row * ld + ia);
+      if (WQ && nv >= 5) {
+        // the owners of the four order statistics (less <= kk < less + eq) publish their key;
+        // four hits per row, so the divergent stores sit behind a wave-uniform test
+        uint32_t hm = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) hm |= ((uint32_t)(kk[j] - less) < (uint32_t)eq ? 1u : 0u) << j;
+        if (key[k] == KEY_SENTINEL) hm = 0;
+        if (__builtin_amdgcn_ballot_w64(hm != 0)) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if ((hm >> j) & 1u) tval[j] = key[k];   // all writers store the same key
+        }
       }
     }
   }
@@ -734,35 +857,62 @@ k_cs_rank_fa(const double* __restrict__ X, double* __restrict__ Y, int64_t D, in
       const uint32_t* nb = ic.nanb + (rw.s + rw.lag[m]) * ic.nw;
 #pragma unroll
       for (int k = 0; k < EMAX; ++k) {
-        const int i = fr_in<NT>(t, k, (int)A) ? t + k * NT : 0;   // unconditional loads
+        const int i = fr_in<NT, EP>(t, k, (int)A) ? t + k * NT : 0;   // unconditional loads
         const uint32_t bit = (nb[i >> 5] >> (i & 31)) & 1u;
-        if (fr_in<NT>(t, k, (int)A) && key[k] != KEY_SENTINEL) em |= bit << (2 * k + m);
+        if (fr_in<NT, EP>(t, k, (int)A) && key[k] != KEY_SENTINEL) em |= bit << (2 * k + m);
       }
     }
   }
   if (WQ) {
     __syncthreads();
-    double lo = qnan(), hi = qnan();
-    if (nv >= 5) {
-      double qv[2];
+    if constexpr (DIET) {
+      // fewer than 5 valid values: winsor is the identity -- infinite bounds clip nothing (and
+      // a NaN compares false), so the output loop has no per-element test of nv
+      double lo = -__builtin_inf(), hi = __builtin_inf();
+      if (nv >= 5) {
+        double qv[2];
 #pragma unroll
-      for (int z = 0; z < 2; ++z) {
-        const double a = okey_inv(tval[2 * z]), b = okey_inv(tval[2 * z + 1]);
-        const double g = gq[z];
-        const double diff = b - a;
-        qv[z] = (g >= 0.5) ? b - diff * (1.0 - g) : a + diff * g;
+        for (int z = 0; z < 2; ++z) {
+          const double a = okey_inv(tval[2 * z]), b = okey_inv(tval[2 * z + 1]);
+          const double g = gq[z];
+          const double diff = b - a;
+          qv[z] = (g >= 0.5) ? b - diff * (1.0 - g) : a + diff * g;
+        }
+        lo = qv[0];
+        hi = qv[1];
       }
-      lo = qv[0];
-      hi = qv[1];
-    }
-    double* y2 = Y2 + row * ld;
+      double* y2 = Y2 + row * ld;
+      const uint32_t ob = (uint32_t)fr_opaque(t) * 8u;
 #pragma unroll
-    for (int k = 0; k < EMAX; ++k) {
-      if (!fr_in<NT>(t, k, (int)A)) continue;
-      const double v = key[k] == KEY_SENTINEL ? qnan() : okey_inv(key[k]);
-      double o = v;
-      if (nv >= 5) o = (v < lo) ? lo : ((v > hi) ? hi : v);
-      __builtin_nontemporal_store((PRES && !((pm >> k) & 1)) ? qnan() : o, y2 + fr_opaque(t) + k * NT);
+      for (int k = 0; k < EMAX; ++k) {
+        if (!fr_in<NT, EMAX>(t, k, (int)A)) continue;
+        const double v = key[k] == KEY_SENTINEL ? qnan() : okey_inv(key[k]);
+        const double o = (v < lo) ? lo : ((v > hi) ? hi : v);
+        __builtin_nontemporal_store(o, fr_at(y2, ob + (uint32_t)(k * NT * 8)));
+      }
+    } else {
+      double lo = qnan(), hi = qnan();
+      if (nv >= 5) {
+        double qv[2];
+#pragma unroll
+        for (int z = 0; z < 2; ++z) {
+          const double a = okey_inv(tval[2 * z]), b = okey_inv(tval[2 * z + 1]);
+          const double g = gq[z];
+          const double diff = b - a;
+          qv[z] = (g >= 0.5) ? b - diff * (1.0 - g) : a + diff * g;
+        }
+        lo = qv[0];
+        hi = qv[1];
+      }
+      double* y2 = Y2 + row * ld;
+#pragma unroll
+      for (int k = 0; k < EMAX; ++k) {
+        if (!fr_in<NT>(t, k, (int)A)) continue;
+        const double v = key[k] == KEY_SENTINEL ? qnan() : okey_inv(key[k]);
+        double o = v;
+        if (nv >= 5) o = (v < lo) ? lo : ((v > hi) ? hi : v);
+        __builtin_nontemporal_store((PRES && !((pm >> k) & 1)) ? qnan() : o, y2 + fr_opaque(t) + k * NT);
+      }
     }
   }
   if constexpr (IC) {
@@ -771,7 +921,7 @@ k_cs_rank_fa(const double* __restrict__ X, double* __restrict__ Y, int64_t D, in
     double* xk = reinterpret_cast<double*>(lds);
 #pragma unroll
     for (int k = 0; k < EMAX; ++k)
-      if (fr_in<NT>(t, k, (int)A)) xk[t + k * NT] = key[k] != KEY_SENTINEL ? okey_inv(key[k]) : 0.0;
+      if (fr_in<NT, EP>(t, k, (int)A)) xk[t + k * NT] = key[k] != KEY_SENTINEL ? okey_inv(key[k]) : 0.0;
     // exposure anchor: a sample key of the row (block-uniform, the sorted samples in tab)
     const uint64_t sk = tab.spl[31] != KEY_SENTINEL ? tab.spl[31] : tab.spl[0];
     const double xs = sk != KEY_SENTINEL ? okey_inv(sk) : 0.0;

@@ -12,6 +12,11 @@
 
 namespace fmx {
 
+// The instantiated element-slot counts of the row kernels, ascending: the launchers take the
+// smallest one that holds the row (br_emax, rank_launch.hpp), and the fused pass derives from
+// the same table which slots are always inside it (fr_emax_prev, rank_fine.hpp).
+constexpr int BR_EMAX_TAB[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 32};
+
 // Development-only phase timer (make prof): thread 0 of every workgroup adds the wall
 // time (100 MHz ticks) of each kernel phase to br_phase_acc[phase].
 #ifdef FMX_PHASE_PROF

@@ -10,8 +10,7 @@ namespace fmx {
 
 static inline int br_emax(int64_t A, int nt) {
   const int64_t e = ceil_div(std::max<int64_t>(A, 1), nt);
-  static const int tab[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 32};
-  for (int v : tab)
+  for (int v : BR_EMAX_TAB)
     if (e <= v && (int64_t)v * nt <= 16384) return v;
   return -1;
 }
