@@ -503,8 +503,9 @@ k_cs_quantile(const double* __restrict__ X, double* __restrict__ Y, int64_t D, i
 
 // ------------------------------------------------------------------------------------
 // Group ops per (date, group): G[d][a] holds dense group ids (-1 = NaN group, dropped by
-// the reference's groupby).  Elements are sorted by (group, key, asset); each group's
-// members are then contiguous and in asset order for the pairwise sums.
+// the reference's groupby; any code outside [0, ngroups) and every absent cell likewise
+// belongs to no group and yields NaN).  Elements are sorted by (group, key, asset); each
+// group's members are then contiguous and in asset order for the pairwise sums.
 template <int OP>
 __global__ void __launch_bounds__(CS_NT)
 k_group(const double* __restrict__ X, const int32_t* __restrict__ G, double* __restrict__ Y, int64_t D,
@@ -528,7 +529,7 @@ k_group(const double* __restrict__ X, const int32_t* __restrict__ G, double* __r
     uint16_t gi = 0xffff;
     if (i < A && (prow ? prow[i] != 0 : true)) {
       int gg = g[i];
-      if (gg >= 0) {
+      if (gg >= 0 && gg < ngroups) {                // the int32 code, before it is narrowed
         gi = (uint16_t)gg;
         double t = x[i];
         k = by_value ? (t == t ? okey(t) : KEY_SENTINEL - 1) : 0;
@@ -538,10 +539,10 @@ k_group(const double* __restrict__ X, const int32_t* __restrict__ G, double* __r
     idx[i] = (uint16_t)i;
     grp[i] = gi;
   }
-  // rows outside any group -> NaN
+  // rows outside any group (absent, or a code outside [0, ngroups)) -> NaN
   for (int64_t a = threadIdx.x; a < A; a += CS_NT) {
     bool p = prow ? prow[a] != 0 : true;
-    if (!p || g[a] < 0) y[a] = qnan();
+    if (!p || g[a] < 0 || g[a] >= ngroups) y[a] = qnan();
   }
   bitonic_sort_grp<CS_NT>(keys, idx, grp, P);
   for (int i = threadIdx.x; i < P; i += CS_NT) vals[i] = (grp[i] != 0xffff) ? x[idx[i]] : 0.0;
@@ -1088,7 +1089,8 @@ k_group_long(const double* __restrict__ X, const int32_t* __restrict__ G, double
     const bool in = a < A && (!prow || prow[a]);
     xv[k] = a < A ? x[a] : 0.0;
     gv[k] = in ? g[a] : -1;
-    if (a < A && gv[k] < 0) y[a] = qnan();       // absent row or NaN group
+    if (gv[k] >= ngroups) gv[k] = -1;            // a code past the last group joins none
+    if (a < A && gv[k] < 0) y[a] = qnan();       // absent row, NaN group or code out of range
   }
   uint16_t* slot = (uint16_t*)(gl + Pmax);
   for (int gg = 0; gg < ngroups; ++gg) {

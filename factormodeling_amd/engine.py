@@ -359,18 +359,20 @@ def cs_quantile_op(kind: str, X, qlo: float, qhi: float, present=None, out=None)
 def group_op(op: str, X, G, ngroups: int, method="average", present=None, long_rows=None):
     """Group ops (operations.py:104-168).  Rows past 16,384 assets (or ``long_rows=True``):
     rank from rows sorted by (group, value) in HBM, mean / neutralize / normalize with the
-    members compacted in HBM scratch (fmx_group_op_long)."""
+    members compacted in HBM scratch (fmx_group_op_long).  ``G`` [D][A] int32 is shared by
+    every factor; an absent cell or a code outside [0, ngroups) belongs to no group and
+    yields NaN on every path."""
     X = as3(X)
     _check_panel(X)
     F, D, A = X.shape
     _check_present(present, D, A)
     if G.dtype != torch.int32 or tuple(G.shape) != (D, A):
         raise _lib.FmxError("G must be int32 [D][A]")
-    if op == "rank" and A > 4096 and ngroups > 0:
+    if op == "rank" and A > 4096:
         big = A > FINE_RANK_MAX_A
-        if not big:
-            # codes outside [0, ngroups) belong to no group (the kernel sorts them past the
-            # last boundary); clamp the index so the count never writes out of bounds
+        if not big and ngroups > 0:
+            # codes outside [0, ngroups) belong to no group; clamp the index so the count
+            # never writes out of bounds (ngroups = 0: no group at all, nothing to count)
             ok = (G >= 0) & (G < ngroups)
             if present is not None:
                 ok &= present != 0

@@ -226,10 +226,13 @@ fmx_status fmx_cs_winsor(const double* X, double* Y, int64_t F, int64_t D, int64
 /* cs_filter_center (operations.py:70-75). */
 fmx_status fmx_cs_filter_center(const double* X, double* Y, int64_t F, int64_t D, int64_t A, int64_t ld,
                                 double qlo, double qhi, const uint8_t* present, void* stream);
-/* group ops (operations.py:112-168).  G: device int32[D][ld] dense group ids, -1 = NaN.
+/* group ops (operations.py:112-168).  G: device int32[D][ld] dense group ids, shared by
+ * all F factors; an absent cell or a code outside [0, ngroups) (-1 = the NaN group)
+ * belongs to no group: counted in none, output NaN.  Every output cell is written.
  * Rows up to 4096 assets: whole-row LDS sort; up to 16384: per-group compaction (the rank
  * sorts each group in LDS: groups of <= 8192 members, larger groups come out NaN --
- * factormodeling_amd.engine.group_op checks and raises before the launch).  Rank methods
+ * factormodeling_amd.engine.group_op counts first and takes fmx_group_rank_sorted for
+ * those).  Rank methods
  * average / min / max / first / dense. */
 fmx_status fmx_group_op(int32_t op, const double* X, const int32_t* G, double* Y, int64_t F, int64_t D, int64_t A,
                         int64_t ld, int32_t ngroups, int32_t method, const uint8_t* present, void* stream);

@@ -424,12 +424,16 @@ def test_group_ops_long_rows_vs_oracle(dev, A):
         ref = O.group_rank_normalized(x, g, method=meth)
         assert_close(got.ravel(), ref.ravel(), exact=True, what=f"rank {meth} A={A}")
     # codes >= ngroups belong to no group (no out-of-bounds count on the host):
-    # the valid groups rank exactly as if those cells had a NaN group
+    # the whole output is exactly what it would be had those cells a NaN group (NaN on them)
     G2 = Gd.clone()
     G2[0, :7] = 11
     G2[1, 3] = 40
     g2 = np.where(G2.cpu().numpy() >= 11, np.nan, g)
     got = E.group_op("rank", Xd, G2, 11).cpu().numpy()[0]
     ref = O.group_rank_normalized(x, g2)
-    ok = ~np.isnan(g2)
-    assert_close(got[ok], ref[ok], exact=True, what=f"rank with out-of-range codes A={A}")
+    assert_close(got.ravel(), ref.ravel(), exact=True, what=f"rank with out-of-range codes A={A}")
+    for op, fn in (("mean", O.group_mean), ("neutralize", O.group_neutralize), ("normalize", O.group_normalize)):
+        got = E.group_op(op, Xd, G2, 11).cpu().numpy()[0]
+        with np.errstate(all="ignore"):
+            ref = fn(x, g2)
+        assert_close(got.ravel(), ref.ravel(), exact=True, what=f"{op} with out-of-range codes A={A}")
