@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CS, CSREG, EW, GROUP, RANK, TS, call, ptr, stream_ptr
+from ._lib import CS, CSREG, EW, GROUP, RANK, TS, TSO, TSO_INTERP, call, ptr, stream_ptr
 
 F64 = torch.float64
 
@@ -54,6 +54,27 @@ def ts(op: str, X, window: int, present=None, out=None):
     _check_present(present, D, A)
     Y = _out(X, out)
     call("fmx_ts_op", TS[op], ptr(X), ptr(Y), F, D, A, A, int(window), ptr(present), stream_ptr())
+    return Y
+
+
+def ts_order(op: str, X, window: int, present=None, q=0.5, interpolation="linear", out=None):
+    """Rolling order statistic (fmx_ts_order): ``op`` in min / max / argmin / argmax / median /
+    quantile; ``q`` and ``interpolation`` are read for quantile only."""
+    if op not in TSO:
+        raise ValueError(f"ts_order: unknown op {op!r}")
+    if interpolation not in TSO_INTERP:
+        raise ValueError(f"ts_order: unknown interpolation {interpolation!r}")
+    if op == "quantile" and not 0.0 <= q <= 1.0:
+        raise ValueError(f"quantile value {q} not in [0, 1]")
+    if int(window) < 1:
+        raise ValueError("window must be >= 1")
+    X = as3(X)
+    _check_panel(X)
+    F, D, A = X.shape
+    _check_present(present, D, A)
+    Y = _out(X, out)
+    call("fmx_ts_order", TSO[op], ptr(X), ptr(Y), F, D, A, A, int(window), float(q), TSO_INTERP[interpolation],
+         ptr(present), stream_ptr())
     return Y
 
 

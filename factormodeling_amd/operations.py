@@ -22,7 +22,7 @@ from .profiling import phase
 
 __all__ = [
     "ts_sum", "ts_mean", "ts_std", "ts_zscore", "ts_rank", "ts_diff", "ts_delay", "ts_decay", "ts_backfill",
-    "ts_corr", "cs_rank", "cs_winsor", "cs_filter_center", "cs_zscore", "cs_bool", "cs_mean", "sign", "power",
+    "ts_corr", "ts_min", "ts_max", "ts_argmin", "ts_argmax", "ts_median", "ts_quantile", "cs_rank", "cs_winsor", "cs_filter_center", "cs_zscore", "cs_bool", "cs_mean", "sign", "power",
     "log", "abs_", "clip", "bucket", "group_mean", "group_neutralize", "group_normalize",
     "group_rank_normalized", "market_neutralize", "ts_regression_fast", "cs_regression",
     "cs_regression_multi",
@@ -121,6 +121,42 @@ def ts_corr(x, y, window: int):
     Yd = P.to_device(yv, dev)[0]
 
     return _panel_apply(x, lambda X, p: engine.ts_corr(X, Yd, window, p))
+
+
+# ---- rolling order statistics (builder-defined, no reference counterpart; pinned to pandas) ----
+def ts_min(series, window: int):
+    """Per-symbol ``x.rolling(window).min()``."""
+    return _panel_apply(series, lambda X, p: engine.ts_order("min", X, window, p))
+
+
+def ts_max(series, window: int):
+    """Per-symbol ``x.rolling(window).max()``."""
+    return _panel_apply(series, lambda X, p: engine.ts_order("max", X, window, p))
+
+
+def ts_argmin(series, window: int):
+    """Rows back from the current row to the window's minimum (0.0 = the current row; ties go
+    to the most recent row); NaN unless the window holds ``window`` non-NaN rows."""
+    return _panel_apply(series, lambda X, p: engine.ts_order("argmin", X, window, p))
+
+
+def ts_argmax(series, window: int):
+    """Rows back from the current row to the window's maximum (see ts_argmin)."""
+    return _panel_apply(series, lambda X, p: engine.ts_order("argmax", X, window, p))
+
+
+def ts_median(series, window: int):
+    """Per-symbol ``x.rolling(window).median()``."""
+    return _panel_apply(series, lambda X, p: engine.ts_order("median", X, window, p))
+
+
+def ts_quantile(series, window: int, q: float, interpolation: str = "linear"):
+    """Per-symbol ``x.rolling(window).quantile(q, interpolation=interpolation)``."""
+    if not 0.0 <= q <= 1.0:
+        raise ValueError(f"quantile value {q} not in [0, 1]")
+    if interpolation not in engine.TSO_INTERP:
+        raise ValueError(f"interpolation {interpolation!r} is not one of {sorted(engine.TSO_INTERP)}")
+    return _panel_apply(series, lambda X, p: engine.ts_order("quantile", X, window, p, q, interpolation))
 
 
 # ========== Cross section (operations.py:53-86) ==========

@@ -60,6 +60,21 @@ typedef int32_t fmx_status;
 #define FMX_TS_DELAY 8    /* operations.py:37  ts_delay    shift(w), w may be <= 0     */
 #define FMX_TS_BACKFILL 9 /* operations.py:50  ts_backfill ffill()                     */
 
+/* rolling order statistics (fmx_ts_order; builder-defined, pandas semantics) */
+#define FMX_TSO_MIN 0      /* ts_min      rolling(w).min()                               */
+#define FMX_TSO_MAX 1      /* ts_max      rolling(w).max()                               */
+#define FMX_TSO_ARGMIN 2   /* ts_argmin   rows back to the window's minimum, latest tie  */
+#define FMX_TSO_ARGMAX 3   /* ts_argmax   rows back to the window's maximum, latest tie  */
+#define FMX_TSO_MEDIAN 4   /* ts_median   rolling(w).median()                            */
+#define FMX_TSO_QUANTILE 5 /* ts_quantile rolling(w).quantile(q, interpolation)          */
+
+/* ts_quantile interpolation (pandas Rolling.quantile(interpolation=...)) */
+#define FMX_TSO_LINEAR 0
+#define FMX_TSO_LOWER 1
+#define FMX_TSO_HIGHER 2
+#define FMX_TSO_MIDPOINT 3
+#define FMX_TSO_NEAREST 4
+
 /* cross-sectional moment ops (fmx_cs_moment) */
 #define FMX_CS_ZSCORE 0            /* operations.py:77  cs_zscore         */
 #define FMX_CS_MEAN 1              /* operations.py:85  cs_mean           */
@@ -120,6 +135,17 @@ fmx_status fmx_ts_op(int32_t op, const double* X, double* Y, int64_t F, int64_t 
 fmx_status fmx_ts_set(const double* X, double* Ymean, double* Ystd, double* Yzscore, double* Yrank, double* Ydecay,
                       int64_t F, int64_t D, int64_t A, int64_t ld, int32_t window, int32_t rank_window,
                       const uint8_t* present, void* stream);
+
+/* Builder-defined rolling order statistics (no reference counterpart): per-symbol
+ * x.rolling(window).min() / .max() / .median() / .quantile(q, interpolation) and, for
+ * FMX_TSO_ARGMIN / ARGMAX, the number of rows back from the current row to the window's
+ * extreme (0.0 = the current row; ties go to the most recent row).  ts_rank's row rule: a
+ * value only where the symbol has `window` present rows ending at the row and none is NaN,
+ * NaN elsewhere.  Results are bit-identical to pandas as values (the sign of a zero result
+ * is unspecified).  Any window >= 1 (no cap), dense or ragged; q in [0, 1] and interp
+ * (FMX_TSO_LINEAR ...) are read for FMX_TSO_QUANTILE only.  Y may not alias X.  No scratch. */
+fmx_status fmx_ts_order(int32_t op, const double* X, double* Y, int64_t F, int64_t D, int64_t A, int64_t ld,
+                        int32_t window, double q, int32_t interp, const uint8_t* present, void* stream);
 
 /* Builder-defined ts_corr (no reference counterpart): per-symbol rolling Pearson of X[f]
  * against Ycol (y_fstride = 0: one [D][ld] series shared by all factors, e.g. returns),
