@@ -169,6 +169,47 @@ def ts_regression(Yv, Xv, valid, window: int, rettype: int):
     return out
 
 
+TS_OLS_MAX_K = 8            # fmx_ts_ols: the (K + 1)(K + 2) / 2 Gram entries live in registers
+TS_OLS_OUTPUTS = ("beta", "alpha", "fitted", "resid", "r2", "sigma")
+
+
+def ts_ols(Y, X, window: int, present=None, intercept=True, shared=False, want=TS_OLS_OUTPUTS):
+    """Rolling multi-factor OLS (fmx_ts_ols): for every column of ``Y`` [Fy][D][A]
+    (or [D][A]) and every symbol and date, the least squares of the symbol's last ``window``
+    valid rows on K regressors -- ``X`` [K][D][A] per symbol or, with ``shared``, a table
+    [K][D] common to all symbols (factor returns).  A row is valid when it is present and y
+    and all K regressors are finite; invalid rows drop out of the symbol's sequence.  Returns
+    a dict of device tensors for the names in ``want``: beta [Fy][K][D][A]; alpha, fitted,
+    resid, r2, sigma [Fy][D][A]; NaN where the row is invalid or the symbol has fewer than
+    ``window`` valid rows so far.  Collinear columns are dropped in column order (beta NaN)."""
+    Y = as3(Y)
+    _check_panel(Y, "Y")
+    Fy, D, A = Y.shape
+    if not isinstance(X, torch.Tensor) or X.device.type != "cuda" or X.dtype != F64 or not X.is_contiguous():
+        raise _lib.FmxError("ts_ols: X must be a contiguous float64 HIP device tensor")
+    if shared:
+        if X.dim() != 2 or X.shape[1] != D:
+            raise _lib.FmxError(f"ts_ols: shared X is {tuple(X.shape)}, expected [K][{D}] to match Y")
+    elif X.dim() != 3 or tuple(X.shape[1:]) != (D, A):
+        raise _lib.FmxError(f"ts_ols: X is {tuple(X.shape)}, expected [K][{D}][{A}] to match Y")
+    K = X.shape[0]
+    _check_present(present, D, A)
+    if not 1 <= K <= TS_OLS_MAX_K:
+        raise _lib.FmxError(f"ts_ols: K = {K} regressors; the kernel takes 1..{TS_OLS_MAX_K}")
+    p = K + int(bool(intercept))
+    if int(window) < p:
+        raise _lib.FmxError(f"ts_ols: window = {window} is shorter than the {p} coefficients")
+    bad = set(want) - set(TS_OLS_OUTPUTS)
+    if bad:
+        raise ValueError(f"ts_ols: unknown outputs {sorted(bad)}")
+    dev = Y.device
+    out = {k: torch.empty((Fy, K, D, A) if k == "beta" else (Fy, D, A), dtype=F64, device=dev) for k in want}
+    work = torch.empty((Fy, D, A), dtype=torch.uint8, device=dev)
+    call("fmx_ts_ols", ptr(Y), ptr(X), ptr(present), Fy, K, D, A, A, int(window), int(bool(intercept)),
+         int(bool(shared)), *(ptr(out.get(k)) for k in TS_OLS_OUTPUTS), ptr(work), stream_ptr())
+    return out
+
+
 # ----------------------------------------------------------------------------- cross section
 def _out(X, out):
     if out is None:

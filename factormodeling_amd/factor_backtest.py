@@ -304,3 +304,24 @@ def cross_sectional_factor_returns(factors_df: pd.DataFrame, returns: pd.Series,
     stats = pd.DataFrame({"alpha": res["alpha"][0].cpu().numpy(), "r2": res["r2"][0].cpu().numpy(),
                           "n": res["n"][0].cpu().numpy()}, index=dates)
     return table, stats
+
+
+def rolling_factor_exposures(returns: pd.Series, factor_ret_df: pd.DataFrame, window: int, intercept: bool = True):
+    """Rolling factor betas per symbol (builder-defined): every symbol's returns regressed on
+    the K factor-return series of ``factor_ret_df`` (a ``dates x factors`` table, exactly what
+    ``cross_sectional_factor_returns`` or ``single_factor_returns`` produce; reindexed to the
+    panel's dates) over the symbol's last ``window`` valid rows, in one ``engine.ts_ols`` call
+    with the table shared by all symbols.  Returns ``(beta, resid, sigma)``: the exposures as a
+    DataFrame on ``returns.index`` with the table's columns, the idiosyncratic return and its
+    rolling volatility (the residual standard error of the window) as Series on the same
+    index; NaN where the row is invalid or the symbol has fewer than ``window`` valid rows."""
+    pi = panel_index(returns.index)
+    dev = device()
+    Y = pi.to_device(returns.to_numpy(dtype=np.float64, na_value=np.nan), dev)
+    tab = factor_ret_df.reindex(pi.dates).to_numpy(dtype=np.float64, na_value=np.nan)
+    X = torch.as_tensor(np.ascontiguousarray(tab.T), device=dev)
+    res = E.ts_ols(Y, X, window, pi.present(dev), intercept, shared=True, want=("beta", "resid", "sigma"))
+    beta = pd.DataFrame(pi.from_device(res["beta"][0]), index=returns.index, columns=factor_ret_df.columns)
+    resid = pd.Series(pi.from_device(res["resid"])[:, 0], index=returns.index, name="resid")
+    sigma = pd.Series(pi.from_device(res["sigma"])[:, 0], index=returns.index, name="sigma")
+    return beta, resid, sigma

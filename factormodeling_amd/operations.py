@@ -25,7 +25,7 @@ __all__ = [
     "ts_corr", "ts_min", "ts_max", "ts_argmin", "ts_argmax", "ts_median", "ts_quantile", "cs_rank", "cs_winsor", "cs_filter_center", "cs_zscore", "cs_bool", "cs_mean", "sign", "power",
     "log", "abs_", "clip", "bucket", "group_mean", "group_neutralize", "group_normalize",
     "group_rank_normalized", "market_neutralize", "ts_regression_fast", "cs_regression",
-    "cs_regression_multi",
+    "cs_regression_multi", "ts_regression_multi",
 ]
 
 
@@ -357,6 +357,54 @@ def cs_regression_multi(y, X, rettype: str = "resid", intercept: bool = True, we
         # the per-date scalar on the rows of the fit: resid is non-NaN exactly there
         res = engine.cs_ols(Yd, Xd, Wd, present, intercept, want=(rettype, "resid"))
         out = torch.where(torch.isnan(res["resid"]), res["resid"], res[rettype].unsqueeze(-1))
+    vals = P.from_device(out)
+    if frame:
+        return pd.DataFrame(vals, index=y.index, columns=y.columns)
+    return pd.Series(vals[:, 0], index=y.index, name=y.name)
+
+
+def ts_regression_multi(y, X, window: int, lag: int = 0, rettype: str = "resid", intercept: bool = True):
+    """Builder-defined (no reference counterpart): rolling per-symbol least squares of ``y`` on
+    the K columns of the DataFrame ``X`` over the symbol's last ``window`` valid rows
+    (``engine.ts_ols``; the rolling counterpart of ``cs_regression_multi``).  ``y`` is a Series
+    or a DataFrame of columns (one batched call).  ``X`` with a (date, symbol) MultiIndex holds
+    per-symbol regressors and is aligned to ``y``'s index; ``X`` with a plain date index holds
+    regressors shared by all symbols (factor returns) and is reindexed to the panel's dates.
+
+    A row is valid when y and every X column are finite; invalid rows drop out of the symbol's
+    sequence (``ts_regression_fast``'s dropna-then-roll, per symbol), and a result exists on a
+    valid row once the symbol has ``window`` valid rows.  Columns collinear with the ones
+    before them inside a window are dropped there.  ``lag`` delays the regressors by ``lag`` of
+    the symbol's OWN rows (``ts_delay``); a shared table is delayed by ``lag`` table rows.  This
+    is NOT the reference's ``x.shift(lag)``, a global row shift that crosses symbols.
+
+    ``rettype`` in resid | fitted | alpha | r2 | sigma returns an object like ``y`` on ``y``'s
+    index, NaN where undefined (nothing is dropped); ``"beta"`` needs a Series ``y`` and
+    returns a DataFrame on ``y.index`` with ``X.columns``."""
+    if rettype not in ("resid", "fitted", "alpha", "r2", "sigma", "beta"):
+        raise ValueError(f"ERROR: rettype={rettype}")
+    if not isinstance(X, pd.DataFrame):
+        raise ValueError("X must be a DataFrame of regressor columns")
+    frame = isinstance(y, pd.DataFrame)
+    if rettype == "beta" and frame:
+        raise ValueError("rettype='beta' needs a Series y (one coefficient table per y column)")
+    if int(lag) < 0:
+        raise ValueError("lag must be >= 0")
+    P = panel_index(y.index)
+    dev = device()
+    Yd = P.to_device(_matrix(y), dev)
+    present = P.present(dev)
+    shared = not isinstance(X.index, pd.MultiIndex)
+    if shared:
+        tab = X.reindex(P.dates).shift(int(lag)).to_numpy(dtype=np.float64, na_value=np.nan)
+        Xd = torch.as_tensor(np.ascontiguousarray(tab.T), device=dev)
+    else:
+        Xd = P.to_device(X.reindex(y.index).to_numpy(dtype=np.float64, na_value=np.nan), dev)
+        if lag:
+            Xd = engine.ts("delay", Xd, int(lag), present)
+    out = engine.ts_ols(Yd, Xd, window, present, intercept, shared, want=(rettype,))[rettype]
+    if rettype == "beta":
+        return pd.DataFrame(P.from_device(out[0]), index=y.index, columns=X.columns)
     vals = P.from_device(out)
     if frame:
         return pd.DataFrame(vals, index=y.index, columns=y.columns)

@@ -700,6 +700,32 @@ fmx_status fmx_cs_ols(const double* Y, const double* X, const double* W, const u
                       int64_t K, int64_t D, int64_t A, int64_t ld, int32_t intercept, double* beta, double* alpha,
                       double* r2, int32_t* n, double* resid, double* fitted, void* stream);
 
+/* ---- rolling multi-factor OLS (builder-defined) ----------------------- */
+/* For every (y column f, asset a, date d): least squares of the column's last `window`
+ * VALID rows ending at d on K regressors.  Row t of column (f, a) is valid when it is present,
+ * Y[f][t][a] is finite and all K regressors of the row are finite; invalid rows drop out of the
+ * column's sequence (dropna, then roll over the surviving rows, per symbol).  An output exists
+ * where row d is valid and the column has `window` valid rows up to and including d; every
+ * output is NaN elsewhere (a window longer than the panel gives all NaN).  The fit is
+ * fmx_cs_ols's with unit weights: means, columns centred in a second pass, G = Xc'Xc scaled to
+ * unit diagonal, Cholesky in column order; column k is DROPPED (beta NaN, no contribution) when
+ * s_k == 0, when (intercept only) s_k <= 1e-13 sqrt(sum x_k^2), or when its pivot is < 1e-10.
+ *   Y [Fy][D][ld]; X [K][D][ld], or with shared != 0 a table [K][D] (the same regressors for
+ *   every symbol, e.g. factor returns); present [D][ld] or NULL.
+ *   beta [Fy][K][D][ld]; alpha (NaN without an intercept), fitted and resid (row d under the
+ *   coefficients of the window ending at d), r2 = 1 - SSR / SST over the window (SST centred
+ *   iff intercept, NaN if SST == 0) and sigma = sqrt(SSR / (window - p_kept)) (p_kept = kept
+ *   columns + intercept; NaN unless window > p_kept): all [Fy][D][ld].  Any may be NULL.
+ *   work: Fy * D * ld bytes of device memory (one validity byte per cell).
+ * Every sum runs over the window oldest row first: a column's bits do not depend on the other
+ * columns of the batch, on the launch or on the run, and a shared table gives the bits of the
+ * same table broadcast to a panel.  1 <= K <= 8, window >= K + intercept, ld >= A, D < 2^31,
+ * non-null panels; anything else is FMX_ERR_ARG before any launch. */
+fmx_status fmx_ts_ols(const double* Y, const double* X, const uint8_t* present, int64_t Fy, int64_t K, int64_t D,
+                      int64_t A, int64_t ld, int32_t window, int32_t intercept, int32_t shared, double* beta,
+                      double* alpha, double* fitted, double* resid, double* r2, double* sigma, uint8_t* work,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
