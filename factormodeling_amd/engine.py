@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CS, CSREG, EW, GROUP, RANK, TS, TSO, TSO_INTERP, call, ptr, stream_ptr
+from ._lib import CS, CSREG, EW, EWM, GROUP, RANK, TS, TSO, TSO_INTERP, call, ptr, stream_ptr
 
 F64 = torch.float64
 
@@ -93,6 +93,42 @@ def ts_set(X, outs: dict, window: int, rank_window: int, present=None):
         raise ValueError(f"ts_set: unsupported ops {sorted(bad)}")
     ps = [ptr(_out(X, outs[k])) if k in outs else None for k in TS_SET]
     call("fmx_ts_set", ptr(X), *ps, F, D, A, A, int(window), int(rank_window), ptr(present), stream_ptr())
+    return outs
+
+
+TS_EWM = tuple(EWM)          # mean var std zscore cov corr, fmx_ts_ewm's argument order
+
+
+def ts_ewm(X, outs: dict, com: float, adjust=True, ignore_na=False, min_periods=0, present=None, y=None):
+    """Exponentially weighted operators (fmx_ts_ewm): ``outs`` maps a subset of TS_EWM to output
+    tensors shaped like X (None: allocated here) and is returned filled.  mean / var / std /
+    zscore share one pass over X; cov / corr need ``y``, a [D][A] series shared by all columns.
+    ``com`` is the centre of mass (alpha = 1 / (1 + com)); pandas' ewm semantics."""
+    bad = set(outs) - set(TS_EWM)
+    if bad:
+        raise ValueError(f"ts_ewm: unsupported outputs {sorted(bad)}")
+    if not outs:
+        raise ValueError("ts_ewm: no output requested")
+    com = float(com)
+    if not com >= 0.0:
+        raise ValueError("ts_ewm: com must be >= 0")
+    if int(min_periods) < 0:
+        raise ValueError("ts_ewm: min_periods must be >= 0")
+    if ("cov" in outs or "corr" in outs) and y is None:
+        raise ValueError("ts_ewm: cov / corr need y")
+    X = as3(X)
+    _check_panel(X)
+    F, D, A = X.shape
+    _check_present(present, D, A)
+    if y is not None:
+        if not isinstance(y, torch.Tensor) or y.device != X.device or y.dtype != F64 or tuple(y.shape) != (D, A):
+            raise _lib.FmxError("y must be a float64 [D][A] tensor on X's device")
+        y = y.contiguous()
+    for k in outs:
+        outs[k] = _out(X, outs[k])
+    ps = [ptr(outs.get(k)) for k in TS_EWM]
+    call("fmx_ts_ewm", ptr(X), ptr(y), *ps, F, D, A, A, com, int(bool(adjust)), int(bool(ignore_na)),
+         int(min_periods), ptr(present), stream_ptr())
     return outs
 
 

@@ -22,7 +22,8 @@ from .profiling import phase
 
 __all__ = [
     "ts_sum", "ts_mean", "ts_std", "ts_zscore", "ts_rank", "ts_diff", "ts_delay", "ts_decay", "ts_backfill",
-    "ts_corr", "ts_min", "ts_max", "ts_argmin", "ts_argmax", "ts_median", "ts_quantile", "cs_rank", "cs_winsor", "cs_filter_center", "cs_zscore", "cs_bool", "cs_mean", "sign", "power",
+    "ts_corr", "ts_min", "ts_max", "ts_argmin", "ts_argmax", "ts_median", "ts_quantile",
+    "ts_ewm_mean", "ts_ewm_var", "ts_ewm_std", "ts_ewm_zscore", "ts_ewm_cov", "ts_ewm_corr", "cs_rank", "cs_winsor", "cs_filter_center", "cs_zscore", "cs_bool", "cs_mean", "sign", "power",
     "log", "abs_", "clip", "bucket", "group_mean", "group_neutralize", "group_normalize",
     "group_rank_normalized", "market_neutralize", "ts_regression_fast", "cs_regression",
     "cs_regression_multi", "ts_regression_multi",
@@ -157,6 +158,78 @@ def ts_quantile(series, window: int, q: float, interpolation: str = "linear"):
     if interpolation not in engine.TSO_INTERP:
         raise ValueError(f"interpolation {interpolation!r} is not one of {sorted(engine.TSO_INTERP)}")
     return _panel_apply(series, lambda X, p: engine.ts_order("quantile", X, window, p, q, interpolation))
+
+
+# ---- exponentially weighted operators (builder-defined, no reference counterpart; pinned to pandas) ----
+def _ewm_com(com=None, span=None, halflife=None, alpha=None) -> float:
+    """The centre of mass of exactly one decay parameter, by pandas' own ranges and arithmetic
+    (pandas.core.window.common.get_center_of_mass): the kernel's alpha = 1 / (1 + com) then
+    carries pandas' rounding."""
+    given = [v is not None for v in (com, span, halflife, alpha)]
+    if sum(given) > 1:
+        raise ValueError("com, span, halflife and alpha are mutually exclusive")
+    if not any(given):
+        raise ValueError("Must pass one of com, span, halflife or alpha")
+    if com is not None:
+        if not com >= 0:
+            raise ValueError("com must satisfy: com >= 0")
+    elif span is not None:
+        if not span >= 1:
+            raise ValueError("span must satisfy: span >= 1")
+        com = (span - 1) / 2
+    elif halflife is not None:
+        if not halflife > 0:
+            raise ValueError("halflife must satisfy: halflife > 0")
+        decay = 1 - np.exp(np.log(0.5) / halflife)
+        com = 1 / decay - 1
+    else:
+        if not 0 < alpha <= 1:
+            raise ValueError("alpha must satisfy: 0 < alpha <= 1")
+        com = (1 - alpha) / alpha
+    return float(com)
+
+
+def _ewm_apply(x, name, y, com, span, halflife, alpha, adjust, ignore_na, min_periods):
+    c = _ewm_com(com, span, halflife, alpha)
+    if int(min_periods) != min_periods or min_periods < 0:
+        raise ValueError("min_periods must be an integer >= 0")
+    Yd = None
+    if y is not None:
+        yv = y.reindex(x.index).to_numpy(dtype=np.float64, na_value=np.nan)
+        Yd = panel_index(x.index).to_device(yv, device())[0]
+    return _panel_apply(x, lambda X, p: engine.ts_ewm(X, {name: None}, c, adjust, ignore_na, int(min_periods),
+                                                      p, Yd)[name])
+
+
+def ts_ewm_mean(x, com=None, span=None, halflife=None, alpha=None, adjust=True, ignore_na=False, min_periods=0):
+    """Per-symbol ``x.ewm(...).mean()``; exactly one of com / span / halflife / alpha."""
+    return _ewm_apply(x, "mean", None, com, span, halflife, alpha, adjust, ignore_na, min_periods)
+
+
+def ts_ewm_var(x, com=None, span=None, halflife=None, alpha=None, adjust=True, ignore_na=False, min_periods=0):
+    """Per-symbol ``x.ewm(...).var()`` (bias=False)."""
+    return _ewm_apply(x, "var", None, com, span, halflife, alpha, adjust, ignore_na, min_periods)
+
+
+def ts_ewm_std(x, com=None, span=None, halflife=None, alpha=None, adjust=True, ignore_na=False, min_periods=0):
+    """Per-symbol ``x.ewm(...).std()`` (bias=False)."""
+    return _ewm_apply(x, "std", None, com, span, halflife, alpha, adjust, ignore_na, min_periods)
+
+
+def ts_ewm_zscore(x, com=None, span=None, halflife=None, alpha=None, adjust=True, ignore_na=False, min_periods=0):
+    """``(x - ts_ewm_mean(x)) / ts_ewm_std(x)`` from one pass over ``x``."""
+    return _ewm_apply(x, "zscore", None, com, span, halflife, alpha, adjust, ignore_na, min_periods)
+
+
+def ts_ewm_cov(x, y, com=None, span=None, halflife=None, alpha=None, adjust=True, ignore_na=False, min_periods=0):
+    """Per-symbol ``x.ewm(...).cov(y)`` (bias=False); ``y`` is a Series aligned to ``x``'s index,
+    shared by all columns of a DataFrame ``x``."""
+    return _ewm_apply(x, "cov", y, com, span, halflife, alpha, adjust, ignore_na, min_periods)
+
+
+def ts_ewm_corr(x, y, com=None, span=None, halflife=None, alpha=None, adjust=True, ignore_na=False, min_periods=0):
+    """Per-symbol ``x.ewm(...).corr(y)``; ``y`` as in ts_ewm_cov."""
+    return _ewm_apply(x, "corr", y, com, span, halflife, alpha, adjust, ignore_na, min_periods)
 
 
 # ========== Cross section (operations.py:53-86) ==========

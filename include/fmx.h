@@ -147,6 +147,30 @@ fmx_status fmx_ts_set(const double* X, double* Ymean, double* Ystd, double* Yzsc
 fmx_status fmx_ts_order(int32_t op, const double* X, double* Y, int64_t F, int64_t D, int64_t A, int64_t ld,
                         int32_t window, double q, int32_t interp, const uint8_t* present, void* stream);
 
+/* Builder-defined exponentially weighted operators (no reference counterpart): per symbol,
+ * over its own rows in date order, x.ewm(com, adjust, ignore_na, min_periods).mean() / .var()
+ * / .std() / .cov(y) / .corr(y) of pandas 2.3 (bias=False for var / std / cov), bit-identical
+ * as values, and zscore = (x - mean) / std in IEEE double.  Outputs are [F][D][ld]; a NULL
+ * output is not computed (FMX_EWM_* name them in argument order).  mean / var / std / zscore
+ * come from ONE pass over X sharing one state (mean alone runs a smaller one); cov / corr take
+ * one more pass and need Ycol, one [D][ld] series shared by all F columns.  com >= 0 is the
+ * centre of mass (alpha = 1 / (1 + com) in double; span, halflife and alpha are converted by
+ * the caller as pandas does); min_periods 0 behaves as 1.  +-inf count as NaN.  An absent
+ * cell (present == 0) is no row of its symbol: it decays nothing and its output is NaN; a
+ * present NaN row decays the weights unless ignore_na.  No output may alias X or Ycol.  No
+ * scratch.  A null panel, ld < A, com < 0 or NaN, min_periods < 0, cov / corr without Ycol
+ * and a call with no output are refused before any device work. */
+#define FMX_EWM_MEAN 0
+#define FMX_EWM_VAR 1
+#define FMX_EWM_STD 2
+#define FMX_EWM_ZSCORE 3
+#define FMX_EWM_COV 4
+#define FMX_EWM_CORR 5
+fmx_status fmx_ts_ewm(const double* X, const double* Ycol, double* Omean, double* Ovar, double* Ostd,
+                      double* Ozscore, double* Ocov, double* Ocorr, int64_t F, int64_t D, int64_t A, int64_t ld,
+                      double com, int32_t adjust, int32_t ignore_na, int32_t min_periods, const uint8_t* present,
+                      void* stream);
+
 /* Builder-defined ts_corr (no reference counterpart): per-symbol rolling Pearson of X[f]
  * against Ycol (y_fstride = 0: one [D][ld] series shared by all factors, e.g. returns),
  * pandas Rolling.corr semantics, min_periods = window. */
