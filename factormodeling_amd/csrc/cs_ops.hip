@@ -196,7 +196,7 @@ constexpr int CSR_ZC_WORDS = 8 * CSR_EL * (CSR_NT / 8) / 32;   // bit words of t
 template <int OP, int NT = CSR_NT>
 __global__ void __launch_bounds__(NT, OP == FMX_CS_GRAM_Z ? 4 * NT / NT : 8)
 k_cs_moment_rg(const double* __restrict__ X, double* __restrict__ Y, int64_t nrows, int64_t A, int64_t ld,
-               PwTable pw, int slen, double* __restrict__ stats, double* __restrict__ Y2, int nts, CsrZc zc) {
+               PwTable pw, int slen, double* __restrict__ stats, double* __restrict__ Y2, CsrZc zc) {
   constexpr int ZCW = 8 * CSR_EL * (NT / 8) / 32;           // bit words of the longest row
   __shared__ int32_t sch[PW_LDS_MAX];
   __shared__ double nodes[2 * (NT / 8) + 8];
@@ -339,10 +339,6 @@ k_cs_moment_rg(const double* __restrict__ X, double* __restrict__ Y, int64_t nro
         return (t - mean) / sd;
       };
       double* y = Y + row * ld;
-      auto put = [&](double v, double* p) {   // nts: write-once outputs as nontemporal stores
-        if (nts) __builtin_nontemporal_store(v, p);
-        else *p = v;
-      };
       // market_neutralize of the same row from the same moments (sd in {0, NaN} -> 0),
       // stored next to each z so no output value stays live across a second loop
       const bool two = OP == FMX_CS_ZSCORE && Y2;
@@ -352,8 +348,8 @@ k_cs_moment_rg(const double* __restrict__ X, double* __restrict__ Y, int64_t nro
       for (int i = 0; i < CSR_EL; ++i)
         if (i < nfull) {
           const double o = outv(xv[i]);
-          put(o, y + st + j + 8 * i);
-          if (two) put(g2 ? 0.0 : o, y2 + st + j + 8 * i);
+          y[st + j + 8 * i] = o;
+          if (two) y2[st + j + 8 * i] = g2 ? 0.0 : o;
         }
       if (act && j == 0)
         for (int q = stop; q < len; ++q) {
@@ -760,8 +756,7 @@ static fmx_status cs_moment_launch(int op, const double* X, double* Y, int64_t F
   FMX_ARG(F * D <= 0x7fffffffll, "too many rows");
   int slen = present ? PW_LDS_MAX + 1 : pw_len((int)A);
   // dense rows whose numpy leaves fit one 512-thread workgroup: register-resident kernel
-  static const bool no_rg = getenv("FMX_CS_MOMENT_LDS") != nullptr;
-  if (!present && slen <= PW_LDS_MAX && !no_rg && A >= 8) {
+  if (!present && slen <= PW_LDS_MAX && A >= 8) {
     std::vector<int32_t> sh(slen);
     fmx_debug_pw_schedule((int32_t)A, sh.data(), slen);
     bool fits = sh[1] > 0 && sh[1] <= CSR_NT / 8;
@@ -788,10 +783,9 @@ static fmx_status cs_moment_launch(int op, const double* X, double* Y, int64_t F
       }
       const int64_t nrows = F * D;
       const int64_t grid = std::min<int64_t>(nrows, slots);
-      static const int nts = getenv("FMX_CS_NT") ? atoi(getenv("FMX_CS_NT")) : 0;   // A/B: nontemporal stores
       CsrZc zc{};
       void* rargs[] = {(void*)&X, (void*)&Y, (void*)&nrows, (void*)&A, (void*)&ld, (void*)&pw, (void*)&slen,
-                       (void*)&stats, (void*)&Y2, (void*)&nts, (void*)&zc};
+                       (void*)&stats, (void*)&Y2, (void*)&zc};
       FMX_HIP(hipLaunchKernel(kr, dim3((unsigned)grid), dim3(CSR_NT), rargs, 0, as_stream(stream)));
       return FMX_OK;
     }
@@ -837,9 +831,8 @@ fmx_status gram_zc_pass(const double* X, int64_t F, int64_t D, int64_t A, int64_
   if (e) return e;
   int slen = pw_len((int)A);
   // rows of <= 32 leaves (A <= ~4096): 256-thread workgroups, every lane holding a leaf's
-  // elements, twice the rows in flight per CU (FMX_GRAM_ZC_NT=512: the A/B arm)
-  static const int want = [] { const char* e = getenv("FMX_GRAM_ZC_NT"); return e ? atoi(e) : 256; }();
-  const bool half = want == 256 && gram_zc_leaves(A) <= 32;
+  // elements, twice the rows in flight per CU
+  const bool half = gram_zc_leaves(A) <= 32;
   const int nt = half ? 256 : CSR_NT;
   const void* kr = half ? (const void*)k_cs_moment_rg<FMX_CS_GRAM_Z, 256> : (const void*)k_cs_moment_rg<FMX_CS_GRAM_Z>;
   static int64_t slots_cache[2] = {0, 0};
@@ -857,9 +850,8 @@ fmx_status gram_zc_pass(const double* X, int64_t F, int64_t D, int64_t A, int64_
   const int64_t grid = std::min<int64_t>(nrows, slots);
   CsrZc zc{Zc, bits, ndc, D, dc0, apad, nd_all, (int)nwd};
   double *Y = nullptr, *stats = nullptr, *Y2 = nullptr;
-  int nts = 0;
   void* rargs[] = {(void*)&X, (void*)&Y, (void*)&nrows, (void*)&A, (void*)&ld, (void*)&pw, (void*)&slen,
-                   (void*)&stats, (void*)&Y2, (void*)&nts, (void*)&zc};
+                   (void*)&stats, (void*)&Y2, (void*)&zc};
   FMX_HIP(hipLaunchKernel(kr, dim3((unsigned)grid), dim3(nt), rargs, 0, as_stream(stream)));
   return FMX_OK;
 }
@@ -1266,13 +1258,7 @@ k_group_xl(const double* __restrict__ X, const int32_t* __restrict__ G, double* 
 }
 
 static int64_t group_xl_grid(int64_t rows) {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      n = 256;
-    return std::max(n, 1);
-  }();
-  return std::max<int64_t>(1, std::min<int64_t>(rows, 2 * (int64_t)cus));
+  return std::max<int64_t>(1, std::min<int64_t>(rows, 2 * (int64_t)device_cu_count()));
 }
 
 extern "C" int64_t fmx_group_op_long_work_bytes(int64_t F, int64_t D, int64_t A) {
@@ -1317,7 +1303,7 @@ extern "C" fmx_status fmx_group_op(int32_t op, const double* X, const int32_t* G
   fmx_status e = FMX_OK;
   PwTable pw = pw_table((int)A, &e);
   if (e) return e;
-  if (A > 4096 && getenv("FMX_GROUP_SORTED") == nullptr) {
+  if (A > 4096) {
     // long rows: per-group compaction (moments) / per-group sort (rank) in one LDS buffer
     FMX_ARG(A <= 16384, "group ops hold one row in registers: A <= 16384");
     // rank: (key, asset) pairs of the largest group, sorted in LDS (<= 8192 members)

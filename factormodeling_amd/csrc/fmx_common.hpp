@@ -133,4 +133,16 @@ inline dim3 fmx_grid2(int64_t inner, int64_t outer) { return dim3((unsigned)inne
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// CU count of the current device, queried once per process; 256 if the query fails.
+inline int device_cu_count() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      n = 256;
+    return n > 1 ? n : 1;
+  }();
+  return cus;
+}
+
 }  // namespace fmx

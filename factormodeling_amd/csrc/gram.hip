@@ -354,8 +354,7 @@ typedef float flt4 __attribute__((ext_vector_type(4)));
 template <int NB, int MODE>   // MODE 0: G = Z Z^T on fp64 MFMA; 1: N = M M^T on bf16 MFMA
 __global__ void __launch_bounds__(SG_NT)
 k_gram_small(const double* __restrict__ X, const double* __restrict__ stats, int64_t F, int64_t D, int64_t A,
-             int64_t ld, int64_t d0, int64_t d1, int64_t dps, double* __restrict__ part,
-             uint32_t* __restrict__ mbits) {
+             int64_t ld, int64_t d0, int64_t d1, int64_t dps, double* __restrict__ part) {
   constexpr int FP = 16 * NB;
   constexpr int NTRI = NB * (NB + 1) / 2;
   constexpr int NWV = SG_NT / 64;
@@ -410,10 +409,7 @@ k_gram_small(const double* __restrict__ X, const double* __restrict__ stats, int
     issue();
     load_stats(ds);
   }
-  // mask word of chunk c for row r: mword * F + r, word-major so that a chunk's rows are
-  // one contiguous run (32-bit: F * dates * A/32 < 2^32)
-  uint32_t mword = (uint32_t)((ds - d0) * nch);
-  int64_t cin = 0, dcur = ds;                    // chunk c's asset block and date
+  int64_t cin = 0, dcur = ds;                   // chunk c's asset block and date
   __syncthreads();
   for (int64_t c = 0; c < total; ++c) {
 #pragma unroll
@@ -424,12 +420,6 @@ k_gram_small(const double* __restrict__ X, const double* __restrict__ stats, int
       const bool ok = (v == v) && (sd > 0.0);
       if (MODE == 0) Zs[r * SG_KP + cl] = ok ? (v - mu_s[r]) / sd : 0.0;
       else Ms[r * SG_MP + cl] = ok ? (uint16_t)0x3f80 : (uint16_t)0;   // bf16 1.0 / 0.0
-      if (MODE == 0 && mbits) {
-        // the chunk's validity bits, one 32-asset word per row (lanes 0-31: row r, 32-63:
-        // row r+1): the pair counts N = M M^T come from these by AND + popcount
-        const uint64_t bal = __ballot(ok);
-        if ((lane & 31) == 0 && r < F) mbits[mword * (uint32_t)F + (uint32_t)r] = (uint32_t)(bal >> lane);
-      }
     }
     __syncthreads();
     if (c + 1 < total) issue();
@@ -458,7 +448,6 @@ k_gram_small(const double* __restrict__ X, const double* __restrict__ stats, int
     }
     // the stats of chunk c were consumed before the barrier above
     if (c + 1 < total && ++cin == nch) { cin = 0; load_stats(++dcur); }
-    ++mword;
     __syncthreads();
   }
   double* p = part + slice * (int64_t)FP * FP;
@@ -512,7 +501,7 @@ template <int NB, bool ZIN, bool UNITS = false>   // ZIN: X holds the z-scores (
 __global__ void __launch_bounds__(GDB_NT) __attribute__((amdgpu_waves_per_eu(GDB_NT / 256, GDB_NT / 256)))
 k_gram_db(const double* __restrict__ X, const double* __restrict__ stats, int64_t F, int64_t D, int64_t A,
           int64_t ld, int64_t d0, int64_t nch, int64_t total, int64_t nslice, double* __restrict__ part,
-          uint32_t* __restrict__ mbits, int opt, int units_per_date = 1) {
+          uint32_t* __restrict__ mbits, int units_per_date = 1) {
   constexpr int FP = 16 * NB;
   constexpr int NTRI = NB * (NB + 1) / 2;
   constexpr int NWV = GDB_NT / 64;
@@ -607,7 +596,7 @@ k_gram_db(const double* __restrict__ X, const double* __restrict__ stats, int64_
   // half the waves of each SIMD (waves s, s+4, s+8, s+12 share SIMD s) run their MFMAs
   // before staging the next chunk and half after, so the SIMD's MFMA pipe is not idle
   // while all four waves do the staging VALU work at the same time
-  const bool mfma_first = (opt & 2) && ((wid >> 2) & 1);
+  const bool mfma_first = (wid >> 2) & 1;
   for (int64_t c = c0; c < c1; ++c) {
     const int b = (int)((c - c0) & 1);
     auto next = [&]() {
@@ -686,23 +675,20 @@ k_gram_db(const double* __restrict__ X, const double* __restrict__ stats, int64_
   }
 }
 
-// Sum the slices in order (deterministic) for the upper-triangle blocks and mirror.
-__global__ void k_gram_small_reduce(const double* __restrict__ partG, const double* __restrict__ partN,
-                                    int64_t nslice, int FP, int64_t F, double* __restrict__ G,
-                                    double* __restrict__ N, int accumulate,
+// Sum the slices in order (deterministic) for the upper-triangle blocks and mirror; the
+// pair counts come from the integer counters.
+__global__ void k_gram_small_reduce(const double* __restrict__ partG, int64_t nslice, int FP, int64_t F,
+                                    double* __restrict__ G, double* __restrict__ N, int accumulate,
                                     const unsigned long long* __restrict__ ncnt) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (int64_t)FP * FP) return;
   const int i = (int)(e / FP), j = (int)(e % FP);
   if ((i >> 4) > (j >> 4) || i >= F || j >= F) return;
   const int64_t st = (int64_t)FP * FP;
-  double g = 0.0, n = 0.0;
+  double g = 0.0;
 #pragma unroll 8
-  for (int64_t sl = 0; sl < nslice; ++sl) {
-    g += partG[sl * st + e];
-    if (!ncnt) n += partN[sl * st + e];
-  }
-  if (ncnt) n = (double)ncnt[e];
+  for (int64_t sl = 0; sl < nslice; ++sl) g += partG[sl * st + e];
+  double n = (double)ncnt[e];
   if (accumulate) {
     g += G[(int64_t)i * F + j];
     n += N[(int64_t)i * F + j];
@@ -769,56 +755,13 @@ k_gram_finalize(const int64_t* __restrict__ limbs, const int64_t* __restrict__ c
   }
 }
 
-// N = M M^T from the validity bits k_gram_small<.,0> packed (32 assets per word, stored
-// word-major [word][F]): one
-// workgroup per (32 x 32 tile of the upper triangle, word range); 64-word chunks of the
-// 64 rows staged in LDS, each thread owns one row i and four rows j.  Integer counts:
-// exact, and order-free (64-bit atomics into ncnt[FP][FP]).
-constexpr int PC_W = 64;
-__global__ void __launch_bounds__(256)
-k_gram_popc(const uint32_t* __restrict__ mbits, int64_t F, int64_t nw, int64_t wps, int FP,
-            unsigned long long* __restrict__ ncnt) {
-  __shared__ uint32_t Ai[32][PC_W + 1], Bj[32][PC_W + 1];
-  const int tid = threadIdx.x;
-  int tt = blockIdx.x, ti = 0;
-  const int T = (int)((F + 31) / 32);
-  while (tt >= T - ti) { tt -= T - ti; ++ti; }
-  const int I0 = ti * 32, J0 = (ti + tt) * 32;
-  const int64_t w0 = (int64_t)blockIdx.y * wps, w1 = min<int64_t>(nw, w0 + wps);
-  const int i = tid >> 3, jg = tid & 7;
-  unsigned acc[4] = {0u, 0u, 0u, 0u};
-  for (int64_t wc = w0; wc < w1; wc += PC_W) {
-    for (int q = tid; q < 32 * PC_W; q += 256) {
-      const int r = q & 31, w = q >> 5;          // word-major bits: 32 rows of a word are contiguous
-      const bool in = wc + w < w1;
-      Ai[r][w] = (in && I0 + r < F) ? mbits[(wc + w) * F + I0 + r] : 0u;
-      Bj[r][w] = (in && J0 + r < F) ? mbits[(wc + w) * F + J0 + r] : 0u;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int w = 0; w < PC_W; ++w) {
-      const uint32_t a = Ai[i][w];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) acc[k] += __popc(a & Bj[jg + 8 * k][w]);
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int gi = I0 + i, gj = J0 + jg + 8 * k;
-    if (gi < F && gj < F && acc[k]) atomicAdd(&ncnt[(int64_t)gi * FP + gj], (unsigned long long)acc[k]);
-  }
-}
-
 // Workspace of the fused F <= 256 Gram (fmx_gram_fused), carved from the caller's buffer:
-// per-slice partial G tiles (and N tiles on the bf16-MFMA A/B path), the validity bits and
-// the 64-bit pair counters.
+// per-slice partial G tiles, the validity bits and the 64-bit pair counters.
 struct SmallPlan {
-  int64_t FP, nslice, dps, nw;
-  bool mask_mfma;
-  int64_t part_bytes() const { return (int64_t)sizeof(double) * FP * FP * nslice * (mask_mfma ? 2 : 1); }
-  int64_t bits_bytes() const { return mask_mfma ? 0 : align256((int64_t)sizeof(uint32_t) * nw * FPF); }
-  int64_t cnt_bytes() const { return mask_mfma ? 0 : (int64_t)sizeof(unsigned long long) * FP * FP; }
+  int64_t FP, nslice, nw;
+  int64_t part_bytes() const { return (int64_t)sizeof(double) * FP * FP * nslice; }
+  int64_t bits_bytes() const { return align256((int64_t)sizeof(uint32_t) * nw * FPF); }
+  int64_t cnt_bytes() const { return (int64_t)sizeof(unsigned long long) * FP * FP; }
   int64_t bytes() const { return align256(part_bytes()) + bits_bytes() + cnt_bytes(); }
   int64_t FPF;   // F (rows of the bit matrix)
   static int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
@@ -827,26 +770,9 @@ static SmallPlan small_plan(int64_t F, int64_t A, int64_t d0, int64_t d1) {
   SmallPlan p;
   p.FP = 16 * ceil_div(std::max<int64_t>(F, 1), 16);
   p.FPF = F;
-  const int64_t ndates = std::max<int64_t>(d1 - d0, 1);
-  p.nslice = std::min<int64_t>(ndates, 512);
-  p.dps = ceil_div(ndates, p.nslice);
-  p.nslice = ceil_div(ndates, p.dps);
-  // pair counts: validity bits packed by the fp64 pass + AND/popcount (default), or the
-  // bf16 MFMA pass over the panel (FMX_GRAM_MASK_MFMA=1, kept for A/B)
-  static const bool mask_mfma = getenv("FMX_GRAM_MASK_MFMA") != nullptr;
-  p.mask_mfma = mask_mfma;
   p.nw = std::max<int64_t>(d1 - d0, 0) * ceil_div(A, (int64_t)SG_K);
-  if (!mask_mfma) {
-    // k_gram_db: one slice (workgroup) per CU over equal ranges of the nw chunks
-    static const int cus = [] {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        n = 256;
-      return std::max(n, 1);
-    }();
-    p.nslice = std::max<int64_t>(1, std::min<int64_t>(p.nw, cus));
-    p.dps = 0;
-  }
+  // k_gram_db: one slice (workgroup) per CU over equal ranges of the nw chunks
+  p.nslice = std::max<int64_t>(1, std::min<int64_t>(p.nw, device_cu_count()));
   return p;
 }
 
@@ -862,45 +788,23 @@ static fmx_status gram_small_launch(const double* X, const double* stats, double
                                     char* work, hipStream_t st) {
   constexpr int FP = 16 * NB;
   const SmallPlan pl = small_plan(F, A, d0, d1);
-  const int64_t nslice = pl.nslice, dps = pl.dps, nw = pl.nw;
-  const int64_t st_elems = (int64_t)FP * FP * nslice;
-  const bool mask_mfma = pl.mask_mfma;
+  const int64_t nslice = pl.nslice, nw = pl.nw;
   double* part = reinterpret_cast<double*>(work);
-  uint32_t* mbits = mask_mfma ? nullptr : reinterpret_cast<uint32_t*>(work + SmallPlan::align256(pl.part_bytes()));
+  uint32_t* mbits = reinterpret_cast<uint32_t*>(work + SmallPlan::align256(pl.part_bytes()));
   unsigned long long* ncnt =
-      mask_mfma ? nullptr
-                : reinterpret_cast<unsigned long long*>(work + SmallPlan::align256(pl.part_bytes()) + pl.bits_bytes());
-  if (ncnt) FMX_HIP(hipMemsetAsync(ncnt, 0, sizeof(unsigned long long) * FP * FP, st));
-  static const bool db = getenv("FMX_GRAM_SINGLE_BUFFER") == nullptr;   // A/B switch
-  if (!mask_mfma && db) {
-    const int64_t nch = ceil_div(A, (int64_t)SG_K);
-    // bit 1: MFMA / staging interleave across each SIMD's waves (default; A/B switch)
-    static const int gopt = getenv("FMX_GRAM_OPT") ? atoi(getenv("FMX_GRAM_OPT")) : 2;
-    if (stats)
-      k_gram_db<NB, false><<<(unsigned)nslice, GDB_NT, 0, st>>>(X, stats, F, D, A, ld, d0, nch, nw, nslice, part,
-                                                              mbits, gopt);
-    else
-      k_gram_db<NB, true><<<(unsigned)nslice, GDB_NT, 0, st>>>(X, stats, F, D, A, ld, d0, nch, nw, nslice, part,
-                                                             mbits, gopt);
-    FMX_LAUNCH_CHECK("k_gram_db");
-  } else {
-    if (!stats) { set_error("z-score input (stats == NULL) needs the default fused Gram path"); return FMX_ERR_UNSUPPORTED; }
-    const int64_t dps2 = mask_mfma ? dps : ceil_div(d1 - d0, nslice);
-    const int64_t ns2 = mask_mfma ? nslice : ceil_div(d1 - d0, dps2);
-    k_gram_small<NB, 0><<<(unsigned)ns2, SG_NT, 0, st>>>(X, stats, F, D, A, ld, d0, d1, dps2, part, mbits);
-    FMX_LAUNCH_CHECK("k_gram_small<G>");
-    if (!mask_mfma && ns2 < nslice)   // fewer date slices than planned: zero the unused partials
-      FMX_HIP(hipMemsetAsync(part + ns2 * FP * FP, 0, sizeof(double) * (nslice - ns2) * FP * FP, st));
-  }
-  if (mask_mfma) {
-    k_gram_small<NB, 1><<<(unsigned)nslice, SG_NT, 0, st>>>(X, stats, F, D, A, ld, d0, d1, dps, part + st_elems,
-                                                           nullptr);
-    FMX_LAUNCH_CHECK("k_gram_small<N>");
-  } else if (nw > 0) {
+      reinterpret_cast<unsigned long long*>(work + SmallPlan::align256(pl.part_bytes()) + pl.bits_bytes());
+  FMX_HIP(hipMemsetAsync(ncnt, 0, sizeof(unsigned long long) * FP * FP, st));
+  const int64_t nch = ceil_div(A, (int64_t)SG_K);
+  if (stats)
+    k_gram_db<NB, false><<<(unsigned)nslice, GDB_NT, 0, st>>>(X, stats, F, D, A, ld, d0, nch, nw, nslice, part, mbits);
+  else
+    k_gram_db<NB, true><<<(unsigned)nslice, GDB_NT, 0, st>>>(X, stats, F, D, A, ld, d0, nch, nw, nslice, part, mbits);
+  FMX_LAUNCH_CHECK("k_gram_db");
+  if (nw > 0) {
     if (fmx_status e = launch_pair_counts_cm(mbits, F, nw, FP, ncnt, st)) return e;
   }
-  k_gram_small_reduce<<<(unsigned)ceil_div((int64_t)FP * FP, 256), 256, 0, st>>>(
-      part, mask_mfma ? part + st_elems : nullptr, nslice, FP, F, G, N, accumulate, mask_mfma ? nullptr : ncnt);
+  k_gram_small_reduce<<<(unsigned)ceil_div((int64_t)FP * FP, 256), 256, 0, st>>>(part, nslice, FP, F, G, N, accumulate,
+                                                                                ncnt);
   FMX_LAUNCH_CHECK("k_gram_small_reduce");
   return FMX_OK;
 }
@@ -944,20 +848,13 @@ static fmx_status gram_exact_launch(const double* X, const double* stats, int64_
   uint32_t* mbits = reinterpret_cast<uint32_t*>(work + pl.part_bytes());
   unsigned long long* ncnt = reinterpret_cast<unsigned long long*>(work + pl.part_bytes() + pl.bits_bytes());
   FMX_HIP(hipMemsetAsync(ncnt, 0, pl.cnt_bytes(), st));
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      n = 256;
-    return std::max(n, 1);
-  }();
-  const int64_t nslice = std::max<int64_t>(1, std::min<int64_t>(pl.nunits, cus));
-  static const int gopt = getenv("FMX_GRAM_OPT") ? atoi(getenv("FMX_GRAM_OPT")) : 2;
+  const int64_t nslice = std::max<int64_t>(1, std::min<int64_t>(pl.nunits, device_cu_count()));
   if (stats)
     k_gram_db<NB, false, true><<<(unsigned)nslice, GDB_NT, 0, st>>>(X, stats, F, D, A, ld, d0, pl.nch, pl.nunits,
-                                                                    nslice, part, mbits, gopt, (int)pl.S);
+                                                                    nslice, part, mbits, (int)pl.S);
   else
     k_gram_db<NB, true, true><<<(unsigned)nslice, GDB_NT, 0, st>>>(X, stats, F, D, A, ld, d0, pl.nch, pl.nunits,
-                                                                   nslice, part, mbits, gopt, (int)pl.S);
+                                                                   nslice, part, mbits, (int)pl.S);
   FMX_LAUNCH_CHECK("k_gram_db<units>");
   {
     const int64_t nw = pl.nw;
@@ -1104,14 +1001,8 @@ static fmx_status gram_rows_launch(const double* X, const int64_t* rows, int64_t
   uint32_t* mbits = reinterpret_cast<uint32_t*>(work + pl.part_bytes());
   unsigned long long* ncnt = reinterpret_cast<unsigned long long*>(work + pl.part_bytes() + pl.bits_bytes());
   FMX_HIP(hipMemsetAsync(ncnt, 0, pl.cnt_bytes(), st));
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      n = 256;
-    return std::max(n, 1);
-  }();
   // equal unit ranges, ~8 workgroups per CU (the units are independent: any cut gives the same partials)
-  const int64_t nslice = std::max<int64_t>(1, std::min<int64_t>(pl.nunits, (int64_t)8 * cus));
+  const int64_t nslice = std::max<int64_t>(1, std::min<int64_t>(pl.nunits, (int64_t)8 * device_cu_count()));
   k_gram_rows<NB><<<(unsigned)nslice, GR_NT, 0, st>>>(X, rows, H, F, D, A, ld, d0, pl.nch, pl.nunits, nslice, part,
                                                      mbits, (int)pl.S);
   FMX_LAUNCH_CHECK("k_gram_rows");
@@ -1282,10 +1173,9 @@ static fmx_status window_prune_launch(const double* X, const double* stats, int6
   FMX_HIP(hipMemcpyAsync(s0, s0_host, sizeof(int32_t) * J, hipMemcpyHostToDevice, st));
   if (nd > 0) {
     // one slice per date: the partials ARE the per-date Grams (G on fp64 MFMA, N on bf16)
-    k_gram_small<NB, 0><<<(unsigned)nd, SG_NT, 0, st>>>(X, stats, F, D, A, ld, d_lo, d_hi, 1, part, nullptr);
+    k_gram_small<NB, 0><<<(unsigned)nd, SG_NT, 0, st>>>(X, stats, F, D, A, ld, d_lo, d_hi, 1, part);
     FMX_LAUNCH_CHECK("k_gram_small<G>");
-    k_gram_small<NB, 1><<<(unsigned)nd, SG_NT, 0, st>>>(X, stats, F, D, A, ld, d_lo, d_hi, 1,
-                                                        part + nd * FP * FP, nullptr);
+    k_gram_small<NB, 1><<<(unsigned)nd, SG_NT, 0, st>>>(X, stats, F, D, A, ld, d_lo, d_hi, 1, part + nd * FP * FP);
     FMX_LAUNCH_CHECK("k_gram_small<N>");
   }
   k_window_prune<<<(unsigned)J, 64, sizeof(int) * F, st>>>(part, part + nd * FP * FP, FP, F, d_lo, nd, W, s0, order,
@@ -1518,8 +1408,8 @@ extern "C" fmx_status fmx_gram(const double* Z, const uint16_t* M, double* G, do
 // (1) validity bits (x not NaN, sigma > 0), factor-major [F][nd][nwd], written by the
 // tile kernel's diagonal tiles while they stage (k_valid_bits: the standalone pass);
 // (2) k_gram_f64w: G on fp64 MFMA with the z-score applied while a chunk is staged (X + the
-// row's (mean, sd) instead of Z); (3) k_gram_popc_fm: N = M M^T as AND + popcount of the
-// bits (exact integers), 64 x 64 tiles, 4 x 4 pairs per thread.
+// row's (mean, sd) instead of Z); (3) k_gram_cnt_i8: N = M M^T from the bits on the i8
+// matrix cores (exact integers).
 namespace fmx {
 
 __global__ void __launch_bounds__(256)
@@ -1570,25 +1460,20 @@ __device__ __forceinline__ void gw_tile(int t, int64_t F, int& bi, int& bj) {
   bj = 2 * bi + t;
 }
 
-// ZC: X is the z pass's Zc chunk [F][nd][A] (z-scores, invalid -> 0, A a multiple of GW_K
-// with zero pads): staged as loaded, no row stats, no validity bits.
-template <bool VEC, bool ZC = false>
+template <bool VEC>
 __global__ void __launch_bounds__(1024)
 k_gram_f64w(const double* __restrict__ X, const double* __restrict__ zst, int64_t F, int64_t D, int64_t A, int64_t ld,
-            int64_t d0, int64_t d1, int64_t dates_per_slice, int64_t phase, int64_t ntile, int64_t nslice, int xcd,
-            int opt, double* __restrict__ part, uint16_t* __restrict__ bits16, int64_t nwd) {
+            int64_t d0, int64_t d1, int64_t dates_per_slice, int64_t phase, int64_t ntile, int64_t nslice,
+            double* __restrict__ part, uint16_t* __restrict__ bits16, int64_t nwd) {
   extern __shared__ double gsm[];             // [2][As (256 x KP) | Bs (128 x KP)]
   constexpr int BUF = (GW_I + GW_J) * GW_KP;
-  // work item = slice * ntile + tile.  xcd: workgroups are dealt round-robin to the 8 XCDs,
-  // so XCD x's k-th workgroup takes item x * per + k -- each XCD walks a contiguous run of
+  // work item = slice * ntile + tile.  Workgroups are dealt round-robin to the 8 XCDs, so
+  // XCD x's k-th workgroup takes item x * per + k -- each XCD walks a contiguous run of
   // items (one date range, neighbouring tiles sharing row panels) and its L2 serves the
-  // shared panels; else item = workgroup id.
-  const int64_t total = ntile * nslice, wg = blockIdx.x + (int64_t)blockIdx.y * gridDim.x;
-  int64_t item = wg;
-  if (xcd == 1) {
-    const int64_t per = (total + 7) / 8;
-    item = (wg % 8) * per + wg / 8;
-  }
+  // shared panels.
+  const int64_t total = ntile * nslice, wg = blockIdx.x;
+  const int64_t per = (total + 7) / 8;
+  const int64_t item = (wg % 8) * per + wg / 8;
   if (item >= total) return;                  // whole workgroup: before any barrier
   const int64_t tile = item % ntile, slice = item / ntile;
   int bi, bj;
@@ -1659,21 +1544,19 @@ k_gram_f64w(const double* __restrict__ X, const double* __restrict__ zst, int64_
 #pragma unroll
       for (int q = 0; q < 2; ++q) rb[q] = (rowB && a0 + bc + q < A32) ? pb[q] : qnan();
     }
-    if constexpr (!ZC) {
-      const double2* z = reinterpret_cast<const double2*>(zst);   // [F][D] (mean, 1/sd or 0)
-      sa = rowA ? z[(int64_t)rA * D + d] : make_double2(0.0, 0.0);
-      sb = rowB ? z[(int64_t)rB * D + d] : make_double2(0.0, 0.0);
-    }
+    const double2* z = reinterpret_cast<const double2*>(zst);   // [F][D] (mean, 1/sd or 0)
+    sa = rowA ? z[(int64_t)rA * D + d] : make_double2(0.0, 0.0);
+    sb = rowB ? z[(int64_t)rB * D + d] : make_double2(0.0, 0.0);
   };
   // validity bits: the diagonal tiles (bj = 2 bi, whose i-rows cover every row once per
   // date) write them while staging -- half-word (16 assets) per row and chunk, in the
-  // factor-major [F][nd][2 nwd] u16 = [F][nd][nwd] u32 layout k_gram_popc_fm reads
+  // factor-major [F][nd][2 nwd] u16 = [F][nd][nwd] u32 layout k_gram_cnt_i8 reads
   const bool wbits = bits16 != nullptr && bj == 2 * bi;
   auto stage = [&](int buf, int64_t) {
     double* As = gsm + buf * BUF;
     double* Bs = As + GW_I * GW_KP;
-    const bool oka = !ZC && sa.y > 0.0, okb = !ZC && sb.y > 0.0;   // 1/sd > 0 <=> sd > 0
-    if (!ZC && wbits) {                                      // workgroup-uniform
+    const bool oka = sa.y > 0.0, okb = sb.y > 0.0;           // 1/sd > 0 <=> sd > 0
+    if (wbits) {                                             // workgroup-uniform
       // the row's 16 bits in (q, lane & 3) order: any asset order shared by every row
       // gives the same AND / popcount pair counts
       uint32_t hw = 0;
@@ -1687,13 +1570,6 @@ k_gram_f64w(const double* __restrict__ X, const double* __restrict__ zst, int64_
       if ((lane & 3) == 0 && rowA) bits16[((int64_t)rA * (d1 - d0) + st_dr) * (2 * nwd) + st_j] = (uint16_t)hw;
     }
     if (++st_j == nch32) { st_j = 0; ++st_dr; }
-    if constexpr (ZC) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) As[ar * GW_KP + ac + q] = rowA ? ra[q] : 0.0;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) Bs[br * GW_KP + bc + q] = rowB ? rb[q] : 0.0;
-      return;
-    }
 #if GW_DIAG == 4
 #pragma unroll
     for (int q = 0; q < 4; ++q) As[ar * GW_KP + ac + q] = ra[q];
@@ -1742,7 +1618,7 @@ k_gram_f64w(const double* __restrict__ X, const double* __restrict__ zst, int64_
   // half the waves of each SIMD (waves s, s+4, s+8, s+12 share SIMD s) stage chunk c+1 and
   // issue chunk c+2's loads before their MFMAs of chunk c, half after: the SIMD's MFMA pipe
   // is fed while the other half does its staging VALU work and waits on its loads
-  const bool stage_first = (opt & 1) && ((wid >> 2) & 1);
+  const bool stage_first = (wid >> 2) & 1;
   for (int64_t c = 0; c < nchunk; ++c) {
     auto next = [&]() {
       if (c + 1 < nchunk) {
@@ -1773,7 +1649,7 @@ k_gram_f64w(const double* __restrict__ X, const double* __restrict__ zst, int64_
 }
 
 // The Zc tile kernel with LDS-DMA staging (global_load_lds_dwordx4): the same 256 x 128 tiles,
-// 16 waves of 64 x 32 sub-tiles and 16-asset chunks as k_gram_f64w<true, true>, but a chunk
+// 16 waves of 64 x 32 sub-tiles and 16-asset chunks as k_gram_f64w, but a chunk
 // goes HBM -> LDS with no VGPRs and no staging instructions, three buffers deep: chunk c + 2
 // is in flight while chunk c is multiplied, each wave retires its own DMA of chunk c + 1 with
 // a counted vmcnt and one raw s_barrier per chunk publishes it to every wave.
@@ -1794,15 +1670,17 @@ k_gram_f64w(const double* __restrict__ X, const double* __restrict__ zst, int64_
 #endif
 constexpr int GZ_BUF = (GW_I + GW_J) * GW_K;                 // doubles per buffer (48 KB)
 constexpr size_t GRAM_Z_LDS = sizeof(double) * 3 * GZ_BUF;     // 144 KB
-// NW = 16: waves as 4 x 4 of 64 x 32 sub-tiles (4 x 2 MFMA blocks, 4 waves per SIMD);
-// NW = 8: 4 x 2 of 64 x 64 (4 x 4 blocks: twice the MFMAs per fragment read, 2 waves per SIMD).
-template <int NW>
-__global__ void __launch_bounds__(NW * 64)
+// 16 waves as 4 x 4 of 64 x 32 sub-tiles (4 x 2 MFMA blocks, 4 waves per SIMD).  (8 waves as
+// 4 x 2 of 64 x 64 -- twice the MFMAs per fragment read, 2 waves per SIMD -- measured slower.)
+constexpr int GZ_NW = 16;
+__global__ void __launch_bounds__(GZ_NW * 64)
 k_gram_zw(const double* __restrict__ Z, int64_t F, int64_t nd, int64_t A, int64_t dps, int64_t phase,
           int64_t ntile, int64_t nslice, double* __restrict__ part) {
+  constexpr int NW = GZ_NW;
   constexpr int WC = NW / 4, NBN = GW_J / WC / 16;           // wave columns, 16-blocks per wave row
   constexpr int PA = (GW_I / 8) / NW, PB = (GW_J / 8) / NW;  // DMA pieces per wave and chunk
   constexpr int NP = PA + PB;
+  static_assert(NP == 3, "wait_dma's vmcnt counts three pieces per chunk");
   extern __shared__ double gsm[];
   const int64_t total = ntile * nslice, wg = blockIdx.x;
   const int64_t per = (total + 7) / 8;
@@ -1857,12 +1735,8 @@ k_gram_zw(const double* __restrict__ Z, int64_t F, int64_t nd, int64_t A, int64_
     }
   };
   auto wait_dma = [&](bool keep) {                 // keep: the newest chunk's NP pieces stay in flight
-    if (keep) {
-      if constexpr (NP == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    if (keep) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
   // fragment reads: row r (r & 15 = lane & 15), k = kk + g: logical slot k >> 1, half g & 1
   const int g = lane >> 4, r16 = lane & 15;
@@ -1991,58 +1865,6 @@ __global__ void k_gram_reduce_w(const double* __restrict__ part, int64_t nslice,
   if (accumulate) s += G[i * F + j];
   G[i * F + j] = s;
   G[j * F + i] = s;
-}
-
-// N[i][j] = sum over the bit words of popcount(bits[i] & bits[j]), factor-major bits
-// [F][nw]: one workgroup per (64 x 64 upper tile, word range); 64-word chunks of the tile's
-// 2 x 64 rows staged in LDS; thread (ty, tx) owns rows ty + 16 r and columns tx + 16 c
-// (4 x 4 pairs: 8 LDS words per 16 AND/popcounts).  64-bit atomics into ncnt[F][F].
-constexpr int PF_T = 64, PF_W = 64;
-__global__ void __launch_bounds__(256)
-k_gram_popc_fm(const uint32_t* __restrict__ bits, int64_t F, int64_t nw, int64_t wps,
-               unsigned long long* __restrict__ ncnt) {
-  __shared__ uint32_t Ai[PF_T][PF_W + 1], Bj[PF_T][PF_W + 1];
-  const int tid = threadIdx.x;
-  int tt = blockIdx.x, ti = 0;
-  const int T = (int)((F + PF_T - 1) / PF_T);
-  while (tt >= T - ti) { tt -= T - ti; ++ti; }
-  const int I0 = ti * PF_T, J0 = (ti + tt) * PF_T;
-  const int64_t w0 = (int64_t)blockIdx.y * wps, w1 = min<int64_t>(nw, w0 + wps);
-  const int ty = tid >> 4, tx = tid & 15;
-  unsigned acc[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[r][c] = 0u;
-  for (int64_t wc = w0; wc < w1; wc += PF_W) {
-    for (int q = tid; q < PF_T * PF_W; q += 256) {
-      const int r = q / PF_W, w = q % PF_W;     // row-contiguous words: coalesced
-      const bool in = wc + w < w1;
-      Ai[r][w] = (in && I0 + r < F) ? bits[(int64_t)(I0 + r) * nw + wc + w] : 0u;
-      Bj[r][w] = (in && J0 + r < F) ? bits[(int64_t)(J0 + r) * nw + wc + w] : 0u;
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int w = 0; w < PF_W; ++w) {
-      uint32_t a[4], b[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) a[r] = Ai[ty + 16 * r][w];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) b[c] = Bj[tx + 16 * c][w];
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[r][c] += __popc(a[r] & b[c]);
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int gi = I0 + ty + 16 * r, gj = J0 + tx + 16 * c;
-      if (gi < F && gj < F && gi <= gj && acc[r][c]) atomicAdd(&ncnt[(int64_t)gi * F + gj], (unsigned long long)acc[r][c]);
-    }
 }
 
 // N = M M^T on the i8 matrix cores (v_mfma_i32_16x16x64_i8): the validity bits expand to 0/1
@@ -2240,20 +2062,9 @@ static DirectPlan direct_plan(int64_t F, int64_t D, int64_t A, int64_t d0, int64
 }
 
 // N = M M^T of the validity bits [F][nw] into ncnt (zeroed by the caller): the i8-MFMA tile
-// kernel, or (FMX_GRAM_CNT=0, the A/B arm) the AND / popcount kernel
+// kernel
 static fmx_status launch_pair_counts(const uint32_t* bits, int64_t F, int64_t nw, unsigned long long* ncnt,
                                      hipStream_t st) {
-  static const int mode = [] { const char* e = getenv("FMX_GRAM_CNT"); return e ? atoi(e) : 1; }();
-  if (mode == 0) {
-    const int T = (int)ceil_div(F, (int64_t)PF_T);
-    const int ntp = T * (T + 1) / 2;
-    // >= ~2048 workgroups: the word range is cut into pieces of whole 64-word chunks
-    const int64_t nks = std::max<int64_t>(1, std::min<int64_t>(ceil_div(nw, (int64_t)4 * PF_W), 2048 / ntp + 1));
-    const int64_t wps = ceil_div(ceil_div(nw, nks), (int64_t)PF_W) * PF_W;
-    k_gram_popc_fm<<<dim3((unsigned)ntp, (unsigned)ceil_div(nw, wps)), 256, 0, st>>>(bits, F, nw, wps, ncnt);
-    FMX_LAUNCH_CHECK("k_gram_popc_fm");
-    return FMX_OK;
-  }
   const int T = (int)ceil_div(F, (int64_t)GC_T);
   const int64_t ntp = (int64_t)T * (T + 1) / 2;
   // word slices: ~2 rounds of 4 workgroups per CU with a full last round, whole 16-word
@@ -2276,20 +2087,9 @@ static fmx_status launch_pair_counts(const uint32_t* bits, int64_t F, int64_t nw
 }
 
 // k_gram_db's counts: chunk-major bits [nw][F] into ncnt [FP][FP], every pair of the 16 x 16
-// blocks on or above the block diagonal (FMX_GRAM_CNT=0: the AND / popcount kernel)
+// blocks on or above the block diagonal
 static fmx_status launch_pair_counts_cm(const uint32_t* mbits, int64_t F, int64_t nw, int FP,
                                         unsigned long long* ncnt, hipStream_t st) {
-  static const int mode = [] { const char* e = getenv("FMX_GRAM_CNT"); return e ? atoi(e) : 1; }();
-  if (mode == 0) {
-    const int T = (int)ceil_div(F, (int64_t)32);
-    const int ntile = T * (T + 1) / 2;
-    const int64_t nks = std::max<int64_t>(1, std::min<int64_t>(ceil_div(nw, (int64_t)4 * PC_W), 2048 / ntile + 1));
-    const int64_t wps = ceil_div(ceil_div(nw, nks), (int64_t)PC_W) * PC_W;
-    const unsigned nky = (unsigned)ceil_div(nw, wps);
-    k_gram_popc<<<dim3((unsigned)ntile, nky), 256, 0, st>>>(mbits, F, nw, wps, FP, ncnt);
-    FMX_LAUNCH_CHECK("k_gram_popc");
-    return FMX_OK;
-  }
   const int T = (int)ceil_div(F, (int64_t)GC_T);
   const int64_t ntp = (int64_t)T * (T + 1) / 2;
   const int64_t nchunk = ceil_div(nw, (int64_t)GC_KW);
@@ -2334,19 +2134,13 @@ extern "C" fmx_status fmx_gram_direct(const double* X, const double* stats, doub
   const size_t lds = GRAM_W_LDS;
   FMX_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int64_t dps = pl.g.dps, ntile = pl.g.ntile, nslice = pl.g.nslice;
-  static const int xcd = [] { const char* e = getenv("FMX_GRAM_XCD"); return e ? atoi(e) : 1; }();
-  int xcd_arg = xcd;
-  const int64_t nwg = xcd == 1 ? 8 * ((ntile * nslice + 7) / 8) : ntile * nslice;
+  const int64_t nwg = 8 * ((ntile * nslice + 7) / 8);     // whole rounds of the 8 XCDs
   uint16_t* bits16 = reinterpret_cast<uint16_t*>(bits);
   int64_t nwd = pl.nwd;
-  static const int wopt = [] { const char* e = getenv("FMX_GRAM_WOPT"); return e ? atoi(e) : 1; }();
-  int wopt_arg = wopt;
   int64_t phase = 0;
   void* args[] = {(void*)&X, (void*)&zst, (void*)&F, (void*)&D, (void*)&A, (void*)&ld, (void*)&d0, (void*)&d1,
-                  (void*)&dps, (void*)&phase, (void*)&ntile, (void*)&nslice, (void*)&xcd_arg, (void*)&wopt_arg,
-                  (void*)&part, (void*)&bits16, (void*)&nwd};
-  const dim3 grid = xcd == 2 ? dim3((unsigned)ntile, (unsigned)nslice) : dim3((unsigned)nwg);
-  FMX_HIP(hipLaunchKernel(k, grid, dim3(1024), args, lds, st));
+                  (void*)&dps, (void*)&phase, (void*)&ntile, (void*)&nslice, (void*)&part, (void*)&bits16, (void*)&nwd};
+  FMX_HIP(hipLaunchKernel(k, dim3((unsigned)nwg), dim3(1024), args, lds, st));
   k_gram_reduce_w<<<dim3((unsigned)pl.g.ntile, GW_I * GW_J / 256), 256, 0, st>>>(part, pl.g.nslice, pl.g.ntile, F,
                                                                                  G, accumulate);
   FMX_LAUNCH_CHECK("k_gram_reduce_w");
@@ -2362,15 +2156,11 @@ extern "C" fmx_status fmx_gram_direct(const double* X, const double* stats, doub
 // fp64 partial tiles fold into fixed-point limbs (exactsum.hpp).  A date shard whose bounds
 // are multiples of the block holds whole blocks, so every block's partial -- and the integer
 // sum over blocks and ranks -- is the same at 1, 2, 4 or 8 GPUs.
-// z-pass mode (default where the row fits the register-resident moment kernel, A <= 8192;
-// FMX_GRAM_ZC=0 keeps the stats + z-while-staging form): the dates run in chunks of
+// z-pass mode (where the row fits the register-resident moment kernel, A <= 8192; longer
+// rows keep the stats + z-while-staging form): the dates run in chunks of
 // zc_slices date blocks -- a z pass (row moments, Zc, validity bits) then the tile kernel on
 // Zc with no staging arithmetic.  32 blocks of C4's 72 tiles make 9 full rounds of the CUs;
 // the Zc chunk is capped at 32 GB (FMX_GRAM_ZC_GB).
-static bool gram_zc_enabled(int64_t A) {
-  static const int on = [] { const char* e = getenv("FMX_GRAM_ZC"); return e ? atoi(e) : 1; }();
-  return on && gram_zc_fits(A);
-}
 static DirectPlan direct_exact_plan(int64_t F, int64_t D, int64_t A, int64_t d0, int64_t d1, int64_t phase,
                                     bool zc = false) {
   DirectPlan p;
@@ -2404,14 +2194,14 @@ static int64_t block_phase(int64_t d_origin, int64_t d0) {
 extern "C" int64_t fmx_gram_direct_exact_work_bytes(int64_t F, int64_t D, int64_t A, int64_t d0, int64_t d1,
                                                     int64_t d_origin) {
   if (F <= 0 || d1 <= d0) return 0;
-  return direct_exact_plan(F, D, A, d0, d1, block_phase(d_origin, d0), gram_zc_enabled(A)).bytes();
+  return direct_exact_plan(F, D, A, d0, d1, block_phase(d_origin, d0), gram_zc_fits(A)).bytes();
 }
 
 extern "C" fmx_status fmx_gram_direct_exact(const double* X, const double* stats, int64_t* limbs, int64_t* counts,
                                             int64_t F, int64_t D, int64_t A, int64_t ld, int64_t d0, int64_t d1,
                                             int64_t d_origin, int32_t accumulate, void* work, int64_t work_bytes,
                                             void* stream) {
-  const bool zc = gram_zc_enabled(A);
+  const bool zc = gram_zc_fits(A);
   FMX_ARG(X && limbs && counts, "null pointer");
   FMX_ARG(F >= 0 && D >= 0 && A >= 0 && ld >= A && d0 >= 0 && d1 <= D && d0 <= d1 && d_origin >= 0, "bad dims");
   FMX_ARG(F <= 65535 && d1 - d0 <= 0x7fffffff && A <= 0x7fffffff, "too many factors / dates / assets");
@@ -2435,13 +2225,8 @@ extern "C" fmx_status fmx_gram_direct_exact(const double* X, const double* stats
     // [d0 + 16 s - phase, d0 + 16 (s + 1) - phase) clipped to [d0, d1)
     double* Zc = zinv;
     const int64_t ntile = pl.g.ntile, nsl = pl.g.nslice, dps = FMX_GRAM_DATE_BLOCK, apad = pl.apad, nwd = pl.nwd;
-    // FMX_GRAM_GLDS: 0 register-staged k_gram_f64w<true, true>, 8 / 16 (default) waves of k_gram_zw
-    static const int glds = [] { const char* e = getenv("FMX_GRAM_GLDS"); return e ? atoi(e) : 16; }();
-    const void* k = glds == 8 ? (const void*)k_gram_zw<8> : glds ? (const void*)k_gram_zw<16>
-                                                                 : (const void*)k_gram_f64w<true, true>;
-    const int nthr = glds == 8 ? 512 : 1024;
-    const size_t klds = glds ? GRAM_Z_LDS : GRAM_W_LDS;
-    FMX_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)klds));
+    const void* k = (const void*)k_gram_zw;
+    FMX_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GRAM_Z_LDS));
     for (int64_t s0 = 0; s0 < nsl; s0 += pl.zc_slices) {
       const int64_t s1 = std::min(nsl, s0 + pl.zc_slices);
       const int64_t dc0 = s0 == 0 ? d0 : d0 + s0 * dps - phase, dc1 = std::min(d1, d0 + s1 * dps - phase);
@@ -2449,18 +2234,12 @@ extern "C" fmx_status fmx_gram_direct_exact(const double* X, const double* stats
       if (fmx_status e = gram_zc_pass(X, F, D, A, ld, dc0, ndc, Zc, apad, bits + (dc0 - d0) * nwd, d1 - d0, nwd, st))
         return e;
       const double* zx = Zc;
-      const double* znull = nullptr;
-      int64_t Dz = ndc, Az = apad, lz = apad, z0 = 0, z1 = ndc, ph = s0 == 0 ? phase : 0, nsc = s1 - s0;
-      int xcd_arg = 1, wopt_arg = 1;
+      int64_t Dz = ndc, Az = apad, ph = s0 == 0 ? phase : 0, nsc = s1 - s0;
       double* pc = part + s0 * ntile * (GW_I * GW_J);
-      uint16_t* nob = nullptr;
       const int64_t nwg = 8 * ((ntile * nsc + 7) / 8);
-      void* args[] = {(void*)&zx, (void*)&znull, (void*)&F, (void*)&Dz, (void*)&Az, (void*)&lz, (void*)&z0, (void*)&z1,
-                      (void*)&dps, (void*)&ph, (void*)&ntile, (void*)&nsc, (void*)&xcd_arg, (void*)&wopt_arg,
-                      (void*)&pc, (void*)&nob, (void*)&nwd};
       void* zargs[] = {(void*)&zx, (void*)&F, (void*)&Dz, (void*)&Az, (void*)&dps, (void*)&ph, (void*)&ntile, (void*)&nsc,
                        (void*)&pc};
-      FMX_HIP(hipLaunchKernel(k, dim3((unsigned)nwg), dim3(nthr), glds ? zargs : args, klds, st));
+      FMX_HIP(hipLaunchKernel(k, dim3((unsigned)nwg), dim3(GZ_NW * 64), zargs, GRAM_Z_LDS, st));
     }
     FMX_HIP(hipMemsetAsync(ncnt, 0, pl.cnt_bytes(), st));
     if (fmx_status e = launch_pair_counts(bits, F, pl.nw, ncnt, st)) return e;
@@ -2480,12 +2259,10 @@ extern "C" fmx_status fmx_gram_direct_exact(const double* X, const double* stats
   const void* k = (ld % 2 == 0) ? (const void*)k_gram_f64w<true> : (const void*)k_gram_f64w<false>;
   FMX_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GRAM_W_LDS));
   int64_t dps = pl.g.dps, ntile = pl.g.ntile, nslice = pl.g.nslice, ph = phase, nwd = pl.nwd;
-  int xcd_arg = 1, wopt_arg = 1;
   const int64_t nwg = 8 * ((ntile * nslice + 7) / 8);
   uint16_t* bits16 = reinterpret_cast<uint16_t*>(bits);
   void* args[] = {(void*)&X, (void*)&zst, (void*)&F, (void*)&D, (void*)&A, (void*)&ld, (void*)&d0, (void*)&d1,
-                  (void*)&dps, (void*)&ph, (void*)&ntile, (void*)&nslice, (void*)&xcd_arg, (void*)&wopt_arg,
-                  (void*)&part, (void*)&bits16, (void*)&nwd};
+                  (void*)&dps, (void*)&ph, (void*)&ntile, (void*)&nslice, (void*)&part, (void*)&bits16, (void*)&nwd};
   FMX_HIP(hipLaunchKernel(k, dim3((unsigned)nwg), dim3(1024), args, GRAM_W_LDS, st));
   FMX_HIP(hipMemsetAsync(ncnt, 0, pl.cnt_bytes(), st));
   if (fmx_status e = launch_pair_counts(bits, F, pl.nw, ncnt, st)) return e;

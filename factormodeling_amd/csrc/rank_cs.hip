@@ -14,8 +14,8 @@ template <int NT, int E> constexpr auto kcrw_pres = k_cs_rank_fa<NT, E, true, tr
 
 fmx_status br_cs_rank(const double* X, double* Y, int64_t F, int64_t D, int64_t A, int64_t ld, int method,
                       const uint8_t* present, hipStream_t st) {
-  const int nt = br_nt(1024);
-  const int nt_fa = fa_nt(A) == 1024 ? 1024 : 512;
+  const int nt = 1024;   // cs_rank's measured best on MI355X at A = 5000
+  const int nt_fa = fa_nt(A);
   const size_t lds_fr = std::max<size_t>((size_t)A * 8, (size_t)FR_CS_WORDS * 4);
   const void* kfr = present ? FMX_EMAX_TABLE(kcr_pres)(nt_fa, br_emax(A, nt_fa))
                             : FMX_EMAX_TABLE(kcr_dense)(nt_fa, br_emax(A, nt_fa));
@@ -45,7 +45,7 @@ fmx_status br_cs_rank(const double* X, double* Y, int64_t F, int64_t D, int64_t 
 // the fine kernel (caller splits).
 fmx_status br_cs_rank_winsor(const double* X, double* Yr, double* Yw, int64_t F, int64_t D, int64_t A, int64_t ld,
                              double qlo, double qhi, const uint8_t* present, fmx_rank2_t* RK, hipStream_t st) {
-  const int nt_fa = fa_nt(A) == 1024 ? 1024 : 512;
+  const int nt_fa = fa_nt(A);
   const size_t lds_fr = std::max<size_t>((size_t)A * 8, (size_t)FR_CS_WORDS * 4);
   const int E = br_emax(A, nt_fa);
   const void* k = present ? FMX_EMAX_TABLE(kcrw_pres)(nt_fa, E) : FMX_EMAX_TABLE(kcrw_dense)(nt_fa, E);

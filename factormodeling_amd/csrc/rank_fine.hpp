@@ -19,7 +19,7 @@ namespace fmx {
 #define FR_FA_WAVES1024 8
 #endif
 #ifndef FR_FA_WAVES
-#define FR_FA_WAVES(NT) ((NT) == 1024 ? FR_FA_WAVES1024 : ((NT) == 640 ? 8 : 6))
+#define FR_FA_WAVES(NT) ((NT) == 1024 ? FR_FA_WAVES1024 : 6)
 #endif
 // ... but no more than the LDS lets in: a row stages up to EMAX*NT 8-byte keys (at least
 // the 32 KB counter array), so long rows (EMAX*NT > 6144) hold one or two rows per CU

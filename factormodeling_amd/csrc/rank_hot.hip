@@ -17,13 +17,13 @@ template <int NT, int E> constexpr auto kcrwz_dense = k_cs_rank_fa<NT, E, false,
 fmx_status br_cs_rank_winsor_zn(const double* X, double* Yr, double* Yw, double* Yz, double* Yn, int64_t F, int64_t D,
                                 int64_t A, int64_t ld, int64_t d0, int64_t d1, double qlo, double qhi,
                                 fmx_rank2_t* RK, PwTable pw, int slen, hipStream_t st) {
-  const int nt_fa = fa_nt(A) == 1024 ? 1024 : 512;
+  const int nt_fa = fa_nt(A);
   const size_t lds_fr = std::max<size_t>((size_t)A * 8, (size_t)FR_CS_WORDS * 4);
   const int E = br_emax(A, nt_fa);
   const void* k = E < 0 ? nullptr : FMX_EMAX_TABLE(kcrwz_dense)(nt_fa, E);
   // rows whose numpy moment tree is complete over 64 leaves (4097..8192 assets, e.g. C2's
   // 5000): the moments combine by shuffles, no serial wave-0 tree walk (block_pw_sum_t64)
-  if (k && nt_fa == 512 && pw_tree64((int)A) && getenv("FMX_ZN_T64") == nullptr) {
+  if (k && nt_fa == 512 && pw_tree64((int)A)) {
     if (E == 10) k = (const void*)k_cs_rank_fa<512, 10, false, true, false, true, true>;
     else if (E == 12) k = (const void*)k_cs_rank_fa<512, 12, false, true, false, true, true>;
     else if (E == 16) k = (const void*)k_cs_rank_fa<512, 16, false, true, false, true, true>;
@@ -65,7 +65,7 @@ static bool rank2_pf_enabled() {
 
 fmx_status br_cs_rank2(const double* X, fmx_rank2_t* RK, int64_t F, int64_t D, int64_t A, int64_t ld, int64_t d0,
                        int64_t d1, hipStream_t st) {
-  const int nt_fa = fa_nt(A) == 1024 ? 1024 : 512;
+  const int nt_fa = fa_nt(A);
   const size_t lds_fr = std::max<size_t>((size_t)A * 8, (size_t)FR_CS_WORDS * 4);
   const int E = br_emax(A, nt_fa);
   const bool whole = d0 == 0 && d1 == D;      // the persistent kernel walks whole panels

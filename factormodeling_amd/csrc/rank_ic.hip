@@ -24,7 +24,7 @@ __global__ void k_ic_empty(double* out, int64_t F, int64_t D, int L0, int L1, in
 fmx_status br_ic_daily(const double* X, const double* R, int64_t F, int64_t D, int64_t A, int64_t ld,
                        const int32_t* lags_host, int n_lags, double* out, hipStream_t st) {
   // 512-thread rows up to 4096 assets (C4's 3000: 20.0 vs 23.7 ms per 252 dates)
-  const int nt = br_nt(A <= 4096 ? 512 : 1024);
+  const int nt = A <= 4096 ? 512 : 1024;
   // counters, then keys [A] + member info [A] + lag masks [A] (k_ic_daily_fr)
   const size_t lds_fr = std::max<size_t>((size_t)(FRG<FR_K_IC>::NB + 1) * 8, (size_t)A * 13 + 16);
   auto fr_table = FMX_EMAX_TABLE(k_ic_daily_fr);
@@ -446,13 +446,7 @@ fmx_status br_ic_ranked(const double* X, const fmx_rank2_t* RK, const double* R,
   int32_t* ovf = npos + D;
   k_nan_positions<<<(unsigned)((D + 3) / 4), 256, 0, st>>>(R, D, A, ld, pos, npos);
   FMX_LAUNCH_CHECK("k_nan_positions");
-  static const int list_grid = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-    return 2 * std::max(cus, 1);              // two 1024-thread rows per CU
-  }();
+  const int list_grid = 2 * device_cu_count();       // two 1024-thread rows per CU
   const unsigned wave_grid = (unsigned)((F * D + ICW_WAVES - 1) / ICW_WAVES);
   for (int base = 0; base < n_lags; base += 2) {
     int NL = std::min(2, n_lags - base);
@@ -524,7 +518,7 @@ template <int NT, int E> constexpr auto kcri = k_cs_rank_fa<NT, E, false, false,
 fmx_status br_cs_rank_winsor_ic(const double* X, double* Yr, double* Yw, const double* R, int64_t F, int64_t D,
                                 int64_t A, int64_t ld, double qlo, double qhi, const int32_t* lags, int n_lags,
                                 fmx_rank2_t* RK, int32_t* work, double* out, hipStream_t st) {
-  const int nt_fa = fa_nt(A) == 1024 ? 1024 : 512;
+  const int nt_fa = fa_nt(A);
   // the rank phase's keys / counters, then (IC tail) the exposures + E tables + partials
   const size_t lds_fr = std::max<size_t>({(size_t)A * 8, (size_t)FR_CS_WORDS * 4, (size_t)fr_ic_lds_bytes(A, nt_fa)});
   const int E = br_emax(A, nt_fa);
@@ -560,13 +554,7 @@ fmx_status br_cs_rank_winsor_ic(const double* X, double* Yr, double* Yw, const d
                   (void*)&Yw, (void*)&qlo, (void*)&qhi, (void*)&RKrow, (void*)&ic, (void*)&zn, (void*)&lcap};
   FMX_HIP(set_dyn_lds(k, ll.bytes));
   FMX_HIP(hipLaunchKernel(k, fmx_grid2(F, D), dim3(nt_fa), args, ll.bytes, st));   // date-major rows
-  static const int list_grid = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-    return 2 * std::max(cus, 1);
-  }();
+  const int list_grid = 2 * device_cu_count();
   const fmx_rank2_t* RKc = RK;
   void* largs[] = {(void*)&X, (void*)&RKc, (void*)&R, (void*)&F, (void*)&D, (void*)&A, (void*)&ld, (void*)&L0,
                    (void*)&L1, (void*)&NL, (void*)&out, (void*)&ovf};

@@ -15,17 +15,6 @@ static inline int br_emax(int64_t A, int nt) {
   return -1;
 }
 
-// Workgroup size of a row kernel: its measured best (cs_rank and the IC 1024, the quantile
-// kernels 512 on MI355X at A = 5000), or FMX_BR_NT=512|1024 for all of them.
-static inline int br_nt(int preferred) {
-  static int forced = [] {
-    const char* e = getenv("FMX_BR_NT");
-    const int v = e ? atoi(e) : 0;
-    return (v == 512 || v == 1024) ? v : 0;
-  }();
-  return forced ? forced : preferred;
-}
-
 // Row-rank implementation: fine buckets (finerank.hpp, default) or splitter buckets
 // (bucketrank.hpp) with FMX_RANK_IMPL=br -- kept for A/B measurements.
 enum { RANK_IMPL_FINE = 0, RANK_IMPL_BR = 1 };
@@ -160,22 +149,7 @@ static inline fmx_status launch_persistent(const void* k, int nt, int64_t nrows,
 // Workgroup size of the aliased-LDS cs_rank kernel for rows of A assets: 512 up to 8192
 // assets, 1024 beyond (a row's keys fill half the CU's LDS there, so 16 waves per row
 // instead of 8 -- C5's 10,000-asset rank pass: 287 -> 142 ms, profiles/r02/c5_h6.log).
-// FMX_FA_NT=512|640|1024 forces one size.
-static inline int fa_nt(int64_t A) {
-  static int v = [] {
-    const char* e = getenv("FMX_FA_NT");
-    const int x = e ? atoi(e) : 0;
-    return (x == 512 || x == 640 || x == 1024) ? x : 0;
-  }();
-  return v ? v : (A > 8192 ? 1024 : 512);
-}
-
-#define FMX_EMAX_TABLE3(KT)                                                  \
-  [](int nt, int E) -> const void* {                                         \
-    if (nt == 512) { FMX_EMAX_CASES(KT, 512) }                               \
-    if (nt == 640) { FMX_EMAX_CASES(KT, 640) }                               \
-    FMX_EMAX_CASES(KT, 1024)                                                 \
-  }
+static inline int fa_nt(int64_t A) { return A > 8192 ? 1024 : 512; }
 
 #define FMX_EMAX_TABLE(KT)                                                   \
   [](int nt, int E) -> const void* {                                         \

@@ -543,7 +543,7 @@ __device__ __forceinline__ void ts_set_step(SetSt& c, double v, double* ring, in
 }
 
 // NT: columns (lanes) per workgroup -- adjacent assets, so one date row of a workgroup is
-// NT * 8 contiguous bytes per stream (FMX_TS_SET_NT=512|1024 for A/B; 256 by default)
+// NT * 8 contiguous bytes per stream (512 and 1024 measured no faster)
 template <int W, int WR, int PF, int NT = 256>
 __global__ void __launch_bounds__(NT, TS_SET_WAVES)
 k_ts_set(const double* __restrict__ X, double* __restrict__ Ym, double* __restrict__ Ys, double* __restrict__ Yz,
@@ -1090,7 +1090,7 @@ struct CfDiagRt {
   __device__ double operator[](int) const { return r; }
 };
 #endif
-template <int PF, bool WC>
+template <bool WC>
 __global__ void __launch_bounds__(256)
 k_ts_corr_feat(const double* __restrict__ X, const double* __restrict__ Ycol, double* __restrict__ C,
                double* __restrict__ Out, int64_t F, int64_t D, int64_t A, int64_t ld, int64_t y_fstride, int W,
@@ -1115,66 +1115,59 @@ k_ts_corr_feat(const double* __restrict__ X, const double* __restrict__ Ycol, do
   VarSt vs;                                       // ts_std(x, W) of the raw x (the feature's)
   int64_t i = 0, cnt = 0;
   bool first = true;
-  // software pipeline: the four loads of date d + PF are issued before date d is computed
-  // (a ring of PF dates in registers), so each wave keeps a date's HBM / MALL latency in
-  // flight across its own arithmetic instead of waiting at the top of every step
-  double nx[PF], ny[PF], nxo[PF], nyo[PF];
-  auto fetch = [&](int64_t d, int s) {
+  // software pipeline: the four loads of date d + 1 are issued before date d is computed, so
+  // each wave keeps a date's HBM / MALL latency in flight across its own arithmetic instead
+  // of waiting at the top of every step (two dates ahead: 130 VGPRs, 3 waves/SIMD, slower)
+  double nx, ny, nxo, nyo;
+  auto fetch = [&](int64_t d) {
     const bool in = d < D, old = in && d >= W;
-    nx[s] = in ? x[d * ld] : 0.0;
-    ny[s] = in ? yc[d * ld] : 0.0;
+    nx = in ? x[d * ld] : 0.0;
+    ny = in ? yc[d * ld] : 0.0;
 #ifdef CF_DIAG_NOOLD
-    nxo[s] = nx[s];                               // diagnostic (wrong results): no leaving-row reads
-    nyo[s] = ny[s];
+    nxo = nx;                                     // diagnostic (wrong results): no leaving-row reads
+    nyo = ny;
     (void)old;
 #else
-    nxo[s] = old ? x[(d - W) * ld] : 0.0;
-    nyo[s] = old ? yc[(d - W) * ld] : 0.0;
+    nxo = old ? x[(d - W) * ld] : 0.0;
+    nyo = old ? yc[(d - W) * ld] : 0.0;
 #endif
   };
-#pragma unroll
-  for (int q = 0; q < PF; ++q) fetch(q, q);
-  for (int64_t d0 = 0; d0 < D; d0 += PF) {
-    double xr[PF], yr[PF], xo[PF], yo[PF];
-#pragma unroll
-    for (int q = 0; q < PF; ++q) {
-      const int64_t d = d0 + q;
-      if (d >= D) break;
-      xr[q] = nx[q]; yr[q] = ny[q]; xo[q] = nxo[q]; yo[q] = nyo[q];
-      fetch(d + PF, q);
-      const double xv = xr[q] + 0.0 * yr[q];
-      const double yv = yr[q] + 0.0 * xr[q];
-      const double pv = xv * yv;
-      if (first) { mxy.init(pv); sx.init(xv); sy.init(yv); vs.init(xr[q]); first = false; }
-      if (i >= W) {
-        const double ox = xo[q] + 0.0 * yo[q], oy = yo[q] + 0.0 * xo[q];
-        mxy.remove(ox * oy); sx.remove_r(ox, rt); sy.remove_r(oy, rt);
-        cnt -= (ox + oy == ox + oy);
-        vs.remove_r(xo[q], rt);
-      }
-      mxy.add(pv); sx.add_r(xv, rt); sy.add_r(yv, rt);
-      cnt += (xv + yv == xv + yv);
-      vs.add_r(xr[q], rt);
-      const double cc = (double)cnt;
-      const double ratio = cnt >= 2 ? mdiv(cc, cc - 1.0, rt[cnt - 1]) : cc / (cc - 1.0);
-      const double num = (mxy.result_r(W, rt) - sx.mean_r(W, rt) * sy.mean_r(W, rt)) * ratio;
-      const double pv2 = sx.var_r(W, 1, rt) * sy.var_r(W, 1, rt);
-      double sg;
-      if constexpr (WC) {
-        const double cq = num / sqrt(pv2);
-        __builtin_nontemporal_store(cq, cp + d * ld);
-        sg = cq > 0.0 ? 1.0 : (cq < 0.0 ? -1.0 : (cq == 0.0 ? 0.0 : cq));
-      } else {
-        // (a sign-only shortcut that skips the sqrt and divide for ordinary num / p measured
-        // neutral, 3.35 vs 3.33 ms per 252 dates: this pass is not bound by those VALU ops)
-        const double cq = num / sqrt(pv2);
-        sg = cq > 0.0 ? 1.0 : (cq < 0.0 ? -1.0 : (cq == 0.0 ? 0.0 : cq));
-      }
-      double sd = zsqrt(vs.var_r(W, 1, rt));
-      if (sd == 0.0) sd = qnan();
-      __builtin_nontemporal_store(sg * (xr[q] / sd), o + d * ld);
-      i += 1;
+  fetch(0);
+  for (int64_t d = 0; d < D; ++d) {
+    const double xr = nx, yr = ny, xo = nxo, yo = nyo;
+    fetch(d + 1);
+    const double xv = xr + 0.0 * yr;
+    const double yv = yr + 0.0 * xr;
+    const double pv = xv * yv;
+    if (first) { mxy.init(pv); sx.init(xv); sy.init(yv); vs.init(xr); first = false; }
+    if (i >= W) {
+      const double ox = xo + 0.0 * yo, oy = yo + 0.0 * xo;
+      mxy.remove(ox * oy); sx.remove_r(ox, rt); sy.remove_r(oy, rt);
+      cnt -= (ox + oy == ox + oy);
+      vs.remove_r(xo, rt);
     }
+    mxy.add(pv); sx.add_r(xv, rt); sy.add_r(yv, rt);
+    cnt += (xv + yv == xv + yv);
+    vs.add_r(xr, rt);
+    const double cc = (double)cnt;
+    const double ratio = cnt >= 2 ? mdiv(cc, cc - 1.0, rt[cnt - 1]) : cc / (cc - 1.0);
+    const double num = (mxy.result_r(W, rt) - sx.mean_r(W, rt) * sy.mean_r(W, rt)) * ratio;
+    const double pv2 = sx.var_r(W, 1, rt) * sy.var_r(W, 1, rt);
+    double sg;
+    if constexpr (WC) {
+      const double cq = num / sqrt(pv2);
+      __builtin_nontemporal_store(cq, cp + d * ld);
+      sg = cq > 0.0 ? 1.0 : (cq < 0.0 ? -1.0 : (cq == 0.0 ? 0.0 : cq));
+    } else {
+      // (a sign-only shortcut that skips the sqrt and divide for ordinary num / p measured
+      // neutral, 3.35 vs 3.33 ms per 252 dates: this pass is not bound by those VALU ops)
+      const double cq = num / sqrt(pv2);
+      sg = cq > 0.0 ? 1.0 : (cq < 0.0 ? -1.0 : (cq == 0.0 ? 0.0 : cq));
+    }
+    double sd = zsqrt(vs.var_r(W, 1, rt));
+    if (sd == 0.0) sd = qnan();
+    __builtin_nontemporal_store(sg * (xr / sd), o + d * ld);
+    i += 1;
   }
 }
 
@@ -1410,25 +1403,18 @@ extern "C" fmx_status fmx_ts_set(const double* X, double* Ymean, double* Ystd, d
   double* outs[5] = {Ymean, Ystd, Yzscore, Yrank, Ydecay};
   for (int k = 0; k < 5; ++k) FMX_ARG(outs[k] != X, "outputs must not alias X");
   if (F == 0 || D == 0 || A == 0) return FMX_OK;
-  if (!present && window == 20 && rank_window == 10 && getenv("FMX_TS_SET_SPLIT") == nullptr) {
+  if (!present && window == 20 && rank_window == 10) {
     void* args[] = {(void*)&X, (void*)&Ymean, (void*)&Ystd, (void*)&Yzscore, (void*)&Yrank, (void*)&Ydecay,
                     (void*)&F, (void*)&D, (void*)&A, (void*)&ld};
-    static const int nt = [] {
-      const char* e = getenv("FMX_TS_SET_NT");
-      const int v = e ? atoi(e) : 256;
-      return (v == 512 || v == 1024) ? v : 256;
-    }();
-    const void* k = nt == 1024 ? (const void*)k_ts_set<20, 10, 5, 1024>
-                    : nt == 512 ? (const void*)k_ts_set<20, 10, 5, 512> : (const void*)k_ts_set<20, 10, 5, 256>;
-    FMX_HIP(hipLaunchKernel(k, dim3((unsigned)ceil_div(F * A, nt)), dim3(nt), args, 0, as_stream(stream)));
+    FMX_HIP(hipLaunchKernel((const void*)k_ts_set<20, 10, 5>, dim3((unsigned)ceil_div(F * A, 256)), dim3(256), args, 0,
+                            as_stream(stream)));
     return FMX_OK;
   }
   // other windows / ragged panels: the three moments from one pair of machines (one pass),
-  // then ts_rank and ts_decay on their own best kernels (any window); FMX_TS_SET_SPLIT=1:
-  // one single-op pass per output (A/B)
+  // then ts_rank and ts_decay on their own best kernels (any window)
   const int32_t ops[5] = {FMX_TS_MEAN, FMX_TS_STD, FMX_TS_ZSCORE, FMX_TS_RANK, FMX_TS_DECAY};
   int k0 = 0;
-  if (getenv("FMX_TS_SET_SPLIT") == nullptr && (Ymean || Ystd || Yzscore)) {
+  if (Ymean || Ystd || Yzscore) {
     int W = window;
     void* args[] = {(void*)&X, (void*)&Ymean, (void*)&Ystd, (void*)&Yzscore, (void*)&F, (void*)&D, (void*)&A,
                     (void*)&ld, (void*)&W, (void*)&present};
@@ -1456,8 +1442,7 @@ extern "C" fmx_status fmx_ts_corr(const double* X, const double* Ycol, double* O
   if (!present) {   // dense: leaving values re-read at d - W
     void* rargs[] = {(void*)&X, (void*)&Ycol, (void*)&Out, (void*)&F, (void*)&D, (void*)&A, (void*)&ld,
                      (void*)&y_fstride, (void*)&W};
-    static const bool v1 = getenv("FMX_TS_CORR_V1") != nullptr;   // A/B: the round-3 kernel
-    if (W <= TSC_MAXW && !v1) {
+    if (W <= TSC_MAXW) {
       int64_t nab = ceil_div(A, 64);
       void* fargs[] = {(void*)&X, (void*)&Ycol, (void*)&Out, (void*)&F, (void*)&D, (void*)&A, (void*)&ld,
                        (void*)&y_fstride, (void*)&W, (void*)&nab};
@@ -1486,8 +1471,7 @@ extern "C" fmx_status fmx_ts_corr_vol_feature(const double* X, const double* C, 
   if (F == 0 || D == 0 || A == 0) return FMX_OK;
   int W = window;
   void* args[] = {(void*)&X, (void*)&C, (void*)&Y, (void*)&F, (void*)&D, (void*)&A, (void*)&ld, (void*)&W};
-  static const bool v1 = getenv("FMX_TS_CORR_V1") != nullptr;   // A/B: IEEE divides
-  const bool fast = W <= TSC_MAXW && !v1;
+  const bool fast = W <= TSC_MAXW;   // longer windows: IEEE divides, no LDS table
   FMX_HIP(hipLaunchKernel(fast ? (const void*)k_ts_cvf_rl<8, true> : (const void*)k_ts_cvf_rl<8, false>,
                           dim3((unsigned)ceil_div(F * A, 256)), dim3(256), args, fast ? sizeof(double) * (W + 1) : 0,
                           as_stream(stream)));
@@ -1506,15 +1490,8 @@ extern "C" fmx_status fmx_ts_corr_feature(const double* X, const double* Ycol, d
   int64_t nab = ceil_div(A, 64);
   void* args[] = {(void*)&X, (void*)&Ycol, (void*)&C, (void*)&Y, (void*)&F, (void*)&D, (void*)&A, (void*)&ld,
                   (void*)&y_fstride, (void*)&W, (void*)&nab};
-  // one date in flight: 106 VGPRs, 4 waves/SIMD (two: 130 VGPRs, 3 waves); FMX_CORR_FEAT_PF=2 for A/B
-  static const bool pf2 = [] {
-    const char* e = getenv("FMX_CORR_FEAT_PF");
-    return e && e[0] == '2';
-  }();
-  const void* k = C ? (pf2 ? (const void*)k_ts_corr_feat<2, true> : (const void*)k_ts_corr_feat<1, true>)
-                    : (pf2 ? (const void*)k_ts_corr_feat<2, false> : (const void*)k_ts_corr_feat<1, false>);
-  FMX_HIP(hipLaunchKernel(k,
-                          dim3((unsigned)(nab * ceil_div(F, 4))), dim3(256), args, sizeof(double) * (W + 1),
+  const void* k = C ? (const void*)k_ts_corr_feat<true> : (const void*)k_ts_corr_feat<false>;
+  FMX_HIP(hipLaunchKernel(k, dim3((unsigned)(nab * ceil_div(F, 4))), dim3(256), args, sizeof(double) * (W + 1),
                           as_stream(stream)));
   return FMX_OK;
 }

@@ -692,6 +692,26 @@ def gram(Z, M=None, d0=0, d1=None):
 
 
 FUSED_GRAM_MAX_F = 256
+GRAM_EXACT_SLOTS = 7            # fmx.h FMX_GRAM_EXACT_SLOTS: 6 payload limbs + flag
+
+
+def _check_stats(stats, F, D):
+    """Row stats given by the caller (None: the callee computes or does not need them)."""
+    if stats is not None and (tuple(stats.shape) != (F, D, 2) or stats.dtype != F64 or not stats.is_contiguous()):
+        raise _lib.FmxError("stats must be a contiguous float64 [F][D][2] device tensor")
+
+
+def _exact_outputs(limbs, counts, n, device, msg):
+    """The exact Gram's (limbs int64 [7][n][n], counts int64 [n][n]): allocated where None,
+    else validated (``msg`` on a mismatch)."""
+    if limbs is None:
+        limbs = torch.empty((GRAM_EXACT_SLOTS, n, n), dtype=torch.int64, device=device)
+    if counts is None:
+        counts = torch.empty((n, n), dtype=torch.int64, device=device)
+    if tuple(limbs.shape) != (GRAM_EXACT_SLOTS, n, n) or limbs.dtype != torch.int64 or not limbs.is_contiguous() \
+            or tuple(counts.shape) != (n, n) or counts.dtype != torch.int64 or not counts.is_contiguous():
+        raise _lib.FmxError(msg)
+    return limbs, counts
 
 
 def gram_fused(X, stats, d0=0, d1=None):
@@ -700,8 +720,7 @@ def gram_fused(X, stats, d0=0, d1=None):
     X = as3(X)
     _check_panel(X)
     F, D, A = X.shape
-    if stats is not None and (tuple(stats.shape) != (F, D, 2) or stats.dtype != F64 or not stats.is_contiguous()):
-        raise _lib.FmxError("stats must be a contiguous float64 [F][D][2] device tensor")
+    _check_stats(stats, F, D)
     d1 = D if d1 is None else d1
     G = torch.empty((F, F), dtype=F64, device=X.device)
     N = torch.empty((F, F), dtype=F64, device=X.device)
@@ -710,9 +729,6 @@ def gram_fused(X, stats, d0=0, d1=None):
     call("fmx_gram_fused", ptr(X), ptr(stats), ptr(G), ptr(N), F, D, A, A, int(d0), int(d1), 0, ptr(work), wb,
          stream_ptr())
     return G, N
-
-
-GRAM_EXACT_SLOTS = 7            # fmx.h FMX_GRAM_EXACT_SLOTS: 6 payload limbs + flag
 
 
 def gram_exact(X, stats=None, d0=0, d1=None, limbs=None, counts=None, accumulate=False):
@@ -725,16 +741,9 @@ def gram_exact(X, stats=None, d0=0, d1=None, limbs=None, counts=None, accumulate
     F, D, A = X.shape
     if F > FUSED_GRAM_MAX_F:
         raise _lib.FmxError("gram_exact: F <= 256")
-    if stats is not None and (tuple(stats.shape) != (F, D, 2) or stats.dtype != F64 or not stats.is_contiguous()):
-        raise _lib.FmxError("stats must be a contiguous float64 [F][D][2] device tensor")
+    _check_stats(stats, F, D)
     d1 = D if d1 is None else d1
-    if limbs is None:
-        limbs = torch.empty((GRAM_EXACT_SLOTS, F, F), dtype=torch.int64, device=X.device)
-    if counts is None:
-        counts = torch.empty((F, F), dtype=torch.int64, device=X.device)
-    if tuple(limbs.shape) != (GRAM_EXACT_SLOTS, F, F) or limbs.dtype != torch.int64 or not limbs.is_contiguous() \
-            or tuple(counts.shape) != (F, F) or counts.dtype != torch.int64 or not counts.is_contiguous():
-        raise _lib.FmxError("gram_exact: limbs int64 [7][F][F], counts int64 [F][F]")
+    limbs, counts = _exact_outputs(limbs, counts, F, X.device, "gram_exact: limbs int64 [7][F][F], counts int64 [F][F]")
     nb = int(_lib.load().fmx_gram_exact_work_bytes(F, D, A, int(d0), int(d1)))
     work, wb = _workspace_bytes(X.device, nb)
     call("fmx_gram_exact", ptr(X), ptr(stats), ptr(limbs), ptr(counts), F, D, A, A, int(d0), int(d1),
@@ -771,13 +780,8 @@ def gram_exact_rows(Z, rows, d0=0, d1=None, limbs=None, counts=None, accumulate=
     if not 1 <= H <= GRAM_HEAD_MAX:
         raise _lib.FmxError(f"gram_exact_rows: 1 <= H <= {GRAM_HEAD_MAX}")
     d1 = D if d1 is None else d1
-    if limbs is None:
-        limbs = torch.empty((GRAM_EXACT_SLOTS, H, H), dtype=torch.int64, device=Z.device)
-    if counts is None:
-        counts = torch.empty((H, H), dtype=torch.int64, device=Z.device)
-    if tuple(limbs.shape) != (GRAM_EXACT_SLOTS, H, H) or limbs.dtype != torch.int64 or not limbs.is_contiguous() \
-            or tuple(counts.shape) != (H, H) or counts.dtype != torch.int64 or not counts.is_contiguous():
-        raise _lib.FmxError("gram_exact_rows: limbs int64 [7][H][H], counts int64 [H][H]")
+    limbs, counts = _exact_outputs(limbs, counts, H, Z.device,
+                                   "gram_exact_rows: limbs int64 [7][H][H], counts int64 [H][H]")
     nb = int(_lib.load().fmx_gram_exact_rows_work_bytes(H, D, A, int(d0), int(d1)))
     work, wb = _workspace_bytes(Z.device, nb)
     call("fmx_gram_exact_rows", ptr(Z), ptr(rows), H, ptr(limbs), ptr(counts), F, D, A, A, int(d0), int(d1),
@@ -792,10 +796,10 @@ def prune_head(limbs, counts, order, F, rho=0.7, top_x=5):
     returns the same list (top_x kept inside the head, or the head is the whole order) --
     else ``kept`` is only its prefix."""
     H = int(limbs.shape[1])
-    if tuple(limbs.shape) != (GRAM_EXACT_SLOTS, H, H) or limbs.dtype != torch.int64 or not limbs.is_contiguous() \
-            or tuple(counts.shape) != (H, H) or counts.dtype != torch.int64 or not counts.is_contiguous() \
-            or not 1 <= H <= GRAM_HEAD_MAX:
-        raise _lib.FmxError("prune_head: limbs int64 [7][H][H], counts int64 [H][H], H <= 64")
+    msg = "prune_head: limbs int64 [7][H][H], counts int64 [H][H], H <= 64"
+    _exact_outputs(limbs, counts, H, limbs.device, msg)
+    if counts is None or not 1 <= H <= GRAM_HEAD_MAX:
+        raise _lib.FmxError(msg)
     ordt = order.to(device=limbs.device, dtype=torch.int64).contiguous()
     lim = max(int(top_x), 1)                        # as greedy_prune: top_x <= 0 keeps one
     cap = min(lim, H)
@@ -846,10 +850,9 @@ def gram_direct(X, d0=0, d1=None, stats=None):
     _check_panel(X)
     F, D, A = X.shape
     d1 = D if d1 is None else d1
+    _check_stats(stats, F, D)
     if stats is None:
         _, stats = cs_moment_stats("stats", X)
-    elif tuple(stats.shape) != (F, D, 2) or stats.dtype != F64 or not stats.is_contiguous():
-        raise _lib.FmxError("stats must be a contiguous float64 [F][D][2] device tensor")
     G = torch.empty((F, F), dtype=F64, device=X.device)
     N = torch.empty((F, F), dtype=F64, device=X.device)
     nb = int(_lib.load().fmx_gram_direct_work_bytes(F, D, A, int(d0), int(d1)))
@@ -872,17 +875,10 @@ def gram_direct_exact(X, d0=0, d1=None, d_origin=0, stats=None, limbs=None, coun
     _check_panel(X)
     F, D, A = X.shape
     d1 = D if d1 is None else d1
-    if stats is None:
-        pass            # the kernel's z pass (or, past its row size, its own stats pass) computes the moments
-    elif tuple(stats.shape) != (F, D, 2) or stats.dtype != F64 or not stats.is_contiguous():
-        raise _lib.FmxError("stats must be a contiguous float64 [F][D][2] device tensor")
-    if limbs is None:
-        limbs = torch.empty((GRAM_EXACT_SLOTS, F, F), dtype=torch.int64, device=X.device)
-    if counts is None:
-        counts = torch.empty((F, F), dtype=torch.int64, device=X.device)
-    if tuple(limbs.shape) != (GRAM_EXACT_SLOTS, F, F) or limbs.dtype != torch.int64 or not limbs.is_contiguous() \
-            or tuple(counts.shape) != (F, F) or counts.dtype != torch.int64 or not counts.is_contiguous():
-        raise _lib.FmxError("gram_direct_exact: limbs int64 [7][F][F], counts int64 [F][F]")
+    # stats None: the kernel's z pass (or, past its row size, its own stats pass) computes the moments
+    _check_stats(stats, F, D)
+    limbs, counts = _exact_outputs(limbs, counts, F, X.device,
+                                   "gram_direct_exact: limbs int64 [7][F][F], counts int64 [F][F]")
     nb = int(_lib.load().fmx_gram_direct_exact_work_bytes(F, D, A, int(d0), int(d1), int(d_origin)))
     work, wb = _workspace_bytes(X.device, nb)
     call("fmx_gram_direct_exact", ptr(X), ptr(stats), ptr(limbs), ptr(counts), F, D, A, A, int(d0), int(d1),
@@ -890,26 +886,17 @@ def gram_direct_exact(X, d0=0, d1=None, d_origin=0, stats=None, limbs=None, coun
     return limbs, counts
 
 
-def gram_wide(X, d0=0, d1=None):
-    """The wide (F > 256) Gram: direct from the panel by default; FMX_GRAM_MATERIALIZE=1
-    selects the date-chunked Z / M path (A/B)."""
-    import os
-    if os.environ.get("FMX_GRAM_MATERIALIZE") == "1":
-        return gram_chunked(X, d0, d1)
-    return gram_direct(X, d0, d1)
-
-
 def corr_matrix(X, d0=0, d1=None, stats=None):
     """Builder-defined factor correlation: C = G / N on fp64 MFMA.  F <= 256
-    takes the fused path (row stats from cs_moment, one pass over X); wider panels
-    materialise Z/M and use the 128x128-tiled kernels."""
+    takes the fused path (row stats from cs_moment, one pass over X); wider panels take
+    the direct tile kernel (gram_direct), also straight from the panel."""
     X = as3(X)
     if X.shape[0] <= FUSED_GRAM_MAX_F:
         if stats is None:
             _, stats = cs_moment_stats("stats", X)
         G, N = gram_fused(X, stats, d0, d1)
     else:
-        G, N = gram_wide(X, d0, d1)
+        G, N = gram_direct(X, d0, d1)
     return torch.where(N > 0, G / N.clamp_min(1.0), torch.zeros_like(G))
 
 

@@ -372,7 +372,7 @@ class EngineBackend:
     # ranks-only pass + wave IC vs the standalone IC kernel at C5's 10,000 assets:
     # 142 + 43 ms vs 226 ms (profiles/r02/c5_h6.log; was 420 + 76 ms before the rank
     # kernel's LDS-aware launch bounds and 1024-thread rows, c5_h1.log)
-    rank_pass_max_a = int(os.environ.get("FMX_RANK_PASS_MAX_A", "16384"))
+    rank_pass_max_a = 16384
 
     @staticmethod
     def cs_rank2(X, rank2, dates=None):
@@ -435,14 +435,12 @@ class EngineBackend:
         """G, N over dates [d0, d1): fused single pass for F <= 256 (from ``z``, the
         step's cs_zscore output, when given), else the wide tiles straight from X."""
         if X.shape[0] <= E.FUSED_GRAM_MAX_F:
-            # the z input needs the default kernel; the A/B switches take the stats path
-            ab = os.environ.get("FMX_GRAM_SINGLE_BUFFER") or os.environ.get("FMX_GRAM_MASK_MFMA")
-            if z is not None and not ab:
+            if z is not None:
                 return E.gram_fused(z, None, d0, d1)
             if stats is None:
                 _, stats = E.cs_moment_stats("stats", X)
             return E.gram_fused(X, stats, d0, d1)
-        return E.gram_wide(X, d0, d1)
+        return E.gram_direct(X, d0, d1)
 
     @staticmethod
     def ts_corr_into(X, R, w, out):

@@ -441,3 +441,37 @@ def test_group_ops_long_rows_vs_oracle(dev, A):
         with np.errstate(all="ignore"):
             ref = fn(x, g2)
         assert_close(got.ravel(), ref.ravel(), exact=True, what=f"{op} with out-of-range codes A={A}")
+
+
+# --------------------------------------------------------------------------- windows past TSC_MAXW
+@pytest.mark.parametrize("panel", ["dense", "early_nan"])
+def test_ts_corr_and_feature_window_past_table(dev, panel):
+    """ts_corr and the corr / vol feature at W = 4097, one past the fast kernels' LDS table of
+    reciprocals (TSC_MAXW = 4096): k_ts_corr_rl<2> and k_ts_cvf_rl<8, false>, the IEEE-divide
+    kernels, reached by the window alone.  A = 70: one full wave and a six-lane tail.
+    ``early_nan``: NaN in x and in the returns on dates 0..5 only, so the first windows are
+    NaN and the later ones finite (NaN over the whole history leaves no finite window)."""
+    import torch
+    import factormodeling_amd.engine as E
+    import oracle.ops as O
+    W, A, F = 4097, 70, 2
+    D = W + 12
+    rng = np.random.default_rng(4097)
+    X = rng.standard_normal((F, D, A))
+    R = 0.01 * rng.standard_normal((D, A))
+    if panel == "early_nan":
+        X[:, :6][rng.random((F, 6, A)) < 0.2] = np.nan
+        R[:6][rng.random((6, A)) < 0.1] = np.nan
+    Xd, Rd = torch.as_tensor(X, device=dev), torch.as_tensor(R, device=dev)
+    Cd = E.ts_corr(Xd, Rd, W)
+    c = Cd.cpu().numpy()
+    v = E.corr_vol_feature(Xd, Cd, W).cpu().numpy()
+    for name, got in (("ts_corr", c), ("feature", v)):
+        fin = np.isfinite(got[:, W - 1:])
+        print(f"{panel} {name}: {int(fin.sum())} of {fin.size} outputs on dates >= W - 1 finite")
+        assert fin.mean() >= 0.5
+    if panel == "early_nan":
+        assert np.isnan(c[:, W - 1]).any() and np.isfinite(c[:, W + 5:]).all()
+    for f in range(F):
+        assert_close(c[f].ravel(), O.ts_corr(X[f], R, W).ravel(), exact=True, what=f"ts_corr W={W}")
+        assert_close(v[f].ravel(), O.corr_vol_feature(X[f], R, W).ravel(), exact=True, what=f"feature W={W}")
