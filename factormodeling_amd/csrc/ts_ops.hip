@@ -25,12 +25,26 @@
 
 namespace fmx {
 
+// The rolling aggregations see +-inf as NaN (pandas Rolling._prep_values replaces +-inf by NaN
+// before every sum / mean / std / apply / corr): one inf empties the W windows that hold it and
+// the column then recovers.  Every machine below and every "NaN in the window" counter tests
+// this instead of v == v; one compare on |v|, false for NaN.  The shift ops (diff, delay,
+// backfill, decay with window < 1) are not aggregations and keep +-inf.
+__device__ __forceinline__ bool fin(double v) { return __builtin_fabs(v) < __builtin_inf(); }
+// v as the aggregation sees it
+__device__ __forceinline__ double prep(double v) { return fin(v) ? v : qnan(); }
+// ts_corr: a row counts when both sides are finite.  pandas forms x + 0 y and y + 0 x (a NaN or
+// inf on either side makes both non-finite) and preps both: the same rows.  One test per pair
+// then serves the five machines and the pair count, which get the step without a test of their
+// own (add_ok / remove_ok); the product x y of a counted pair enters its mean as it is.
+__device__ __forceinline__ bool pair_ok(double x, double y) { return fin(x) && fin(y); }
+
 struct SumSt {
   double s, ca, cr, prev;
   int n, same;                 // counts fit 32 bits (n <= D)
   __device__ void init(double first) { s = ca = cr = 0.0; n = 0; same = 0; prev = first; }
   __device__ void add(double v) {
-    if (v == v) {
+    if (fin(v)) {
       n += 1;
       double y = v - ca, t = s + y;
       ca = t - s - y; s = t;
@@ -39,7 +53,7 @@ struct SumSt {
     }
   }
   __device__ void remove(double v) {
-    if (v == v) {
+    if (fin(v)) {
       n -= 1;
       double y = -v - cr, t = s + y;
       cr = t - s - y; s = t;
@@ -56,23 +70,23 @@ struct MeanSt {
   double s, ca, cr, prev;
   int n, neg, same;
   __device__ void init(double first) { s = ca = cr = 0.0; n = neg = same = 0; prev = first; }
-  __device__ void add(double v) {
-    if (v == v) {
-      n += 1;
-      double y = v - ca, t = s + y;
-      ca = t - s - y; s = t;
-      if (__builtin_signbit(v)) neg += 1;
-      if (v == prev) same += 1; else same = 1;
-      prev = v;
-    }
+  __device__ void add(double v) { if (fin(v)) add_ok(v); }
+  __device__ void remove(double v) { if (fin(v)) remove_ok(v); }
+  // the steps themselves, for a caller that has already decided that v counts (ts_corr: one
+  // test per (x, y) pair for all its machines)
+  __device__ void add_ok(double v) {
+    n += 1;
+    double y = v - ca, t = s + y;
+    ca = t - s - y; s = t;
+    if (__builtin_signbit(v)) neg += 1;
+    if (v == prev) same += 1; else same = 1;
+    prev = v;
   }
-  __device__ void remove(double v) {
-    if (v == v) {
-      n -= 1;
-      double y = -v - cr, t = s + y;
-      cr = t - s - y; s = t;
-      if (__builtin_signbit(v)) neg -= 1;
-    }
+  __device__ void remove_ok(double v) {
+    n -= 1;
+    double y = -v - cr, t = s + y;
+    cr = t - s - y; s = t;
+    if (__builtin_signbit(v)) neg -= 1;
   }
   // result() with the division by the count through mdiv (rt[k] = RN(1 / k), k <= window)
   template <class RT>
@@ -102,8 +116,9 @@ struct VarSt {
   double mean, ssq, n, ca, cr, prev;
   int same;
   __device__ void init(double first) { mean = ssq = n = ca = cr = 0.0; same = 0; prev = first; }
-  __device__ void add(double v) {
-    if (v != v) return;
+  __device__ void add(double v) { if (fin(v)) add_ok(v); }
+  __device__ void remove(double v) { if (fin(v)) remove_ok(v); }
+  __device__ void add_ok(double v) {
     n += 1.0;
     if (v == prev) same += 1; else same = 1;
     prev = v;
@@ -114,26 +129,27 @@ struct VarSt {
     if (n != 0.0) mean = mean + t / n; else mean = 0.0;
     ssq = ssq + (v - pm) * (v - mean);
   }
-  __device__ void remove(double v) {
-    if (v == v) {
-      n -= 1.0;
-      if (n != 0.0) {
-        double pm = mean - cr;
-        double y = v - cr;
-        double t = y - mean;
-        cr = t + mean - y;
-        mean = mean - t / n;
-        ssq = ssq - (v - pm) * (v - mean);
-      } else {
-        mean = 0.0;
-        ssq = 0.0;
-      }
+  __device__ void remove_ok(double v) {
+    n -= 1.0;
+    if (n != 0.0) {
+      double pm = mean - cr;
+      double y = v - cr;
+      double t = y - mean;
+      cr = t + mean - y;
+      mean = mean - t / n;
+      ssq = ssq - (v - pm) * (v - mean);
+    } else {
+      mean = 0.0;
+      ssq = 0.0;
     }
   }
   // add / remove / var with every division by a count through mdiv (rt[k] = RN(1 / k))
   template <class RT>
-  __device__ void add_r(double v, RT rt) {
-    if (v != v) return;
+  __device__ void add_r(double v, RT rt) { if (fin(v)) add_ok_r(v, rt); }
+  template <class RT>
+  __device__ void remove_r(double v, RT rt) { if (fin(v)) remove_ok_r(v, rt); }
+  template <class RT>
+  __device__ void add_ok_r(double v, RT rt) {
     n += 1.0;
     if (v == prev) same += 1; else same = 1;
     prev = v;
@@ -145,20 +161,18 @@ struct VarSt {
     ssq = ssq + (v - pm) * (v - mean);
   }
   template <class RT>
-  __device__ void remove_r(double v, RT rt) {
-    if (v == v) {
-      n -= 1.0;
-      if (n != 0.0) {
-        double pm = mean - cr;
-        double y = v - cr;
-        double t = y - mean;
-        cr = t + mean - y;
-        mean = mean - mdiv(t, n, rt[(int)n]);
-        ssq = ssq - (v - pm) * (v - mean);
-      } else {
-        mean = 0.0;
-        ssq = 0.0;
-      }
+  __device__ void remove_ok_r(double v, RT rt) {
+    n -= 1.0;
+    if (n != 0.0) {
+      double pm = mean - cr;
+      double y = v - cr;
+      double t = y - mean;
+      cr = t + mean - y;
+      mean = mean - mdiv(t, n, rt[(int)n]);
+      ssq = ssq - (v - pm) * (v - mean);
+    } else {
+      mean = 0.0;
+      ssq = 0.0;
     }
   }
   template <class RT>
@@ -181,7 +195,7 @@ struct VarSt {
 };
 
 // One side (x or y) of ts_corr: a MeanSt and a VarSt fed the same values, sharing what the
-// two machines track identically -- the NaN test, the count, the run of equal values and
+// two machines track identically -- the finiteness test, the count, the run of equal values and
 // its value -- so each add / remove does that bookkeeping once.  Every arithmetic step is
 // the two machines' own, in their order (bit-identical results).
 struct MVSt {
@@ -195,40 +209,40 @@ struct MVSt {
     prev = first;
   }
   template <class RT>
-  __device__ void add_r(double v, RT rt) {
-    if (v == v) {
-      n += 1;
-      const double y = v - cam, t = s + y;
-      cam = t - s - y; s = t;
-      if (__builtin_signbit(v)) neg += 1;
-      if (v == prev) same += 1; else same = 1;
-      prev = v;
-      const double pm = mean - cav;
-      const double y2 = v - cav;
-      const double t2 = y2 - mean;
-      cav = t2 + mean - y2;
-      mean = mean + mdiv(t2, (double)n, rt[n]);
-      ssq = ssq + (v - pm) * (v - mean);
-    }
+  __device__ void add_r(double v, RT rt) { if (fin(v)) add_ok_r(v, rt); }
+  template <class RT>
+  __device__ void remove_r(double v, RT rt) { if (fin(v)) remove_ok_r(v, rt); }
+  template <class RT>
+  __device__ void add_ok_r(double v, RT rt) {
+    n += 1;
+    const double y = v - cam, t = s + y;
+    cam = t - s - y; s = t;
+    if (__builtin_signbit(v)) neg += 1;
+    if (v == prev) same += 1; else same = 1;
+    prev = v;
+    const double pm = mean - cav;
+    const double y2 = v - cav;
+    const double t2 = y2 - mean;
+    cav = t2 + mean - y2;
+    mean = mean + mdiv(t2, (double)n, rt[n]);
+    ssq = ssq + (v - pm) * (v - mean);
   }
   template <class RT>
-  __device__ void remove_r(double v, RT rt) {
-    if (v == v) {
-      n -= 1;
-      const double y = -v - crm, t = s + y;
-      crm = t - s - y; s = t;
-      if (__builtin_signbit(v)) neg -= 1;
-      if (n != 0) {
-        const double pm = mean - crv;
-        const double y2 = v - crv;
-        const double t2 = y2 - mean;
-        crv = t2 + mean - y2;
-        mean = mean - mdiv(t2, (double)n, rt[n]);
-        ssq = ssq - (v - pm) * (v - mean);
-      } else {
-        mean = 0.0;
-        ssq = 0.0;
-      }
+  __device__ void remove_ok_r(double v, RT rt) {
+    n -= 1;
+    const double y = -v - crm, t = s + y;
+    crm = t - s - y; s = t;
+    if (__builtin_signbit(v)) neg -= 1;
+    if (n != 0) {
+      const double pm = mean - crv;
+      const double y2 = v - crv;
+      const double t2 = y2 - mean;
+      crv = t2 + mean - y2;
+      mean = mean - mdiv(t2, (double)n, rt[n]);
+      ssq = ssq - (v - pm) * (v - mean);
+    } else {
+      mean = 0.0;
+      ssq = 0.0;
     }
   }
   template <class RT>
@@ -371,8 +385,8 @@ __device__ __forceinline__ double ts_step_reg(ColState& c, double v, double* rin
     if (sd == 0.0) sd = qnan();
     out = (v - m) / sd;
   } else if (OP == FMX_TS_RANK || OP == FMX_TS_DECAY) {
-    if (c.i >= W && old != old) c.nan_in_win -= 1;
-    if (v != v) c.nan_in_win += 1;
+    if (c.i >= W && !fin(old)) c.nan_in_win -= 1;
+    if (!fin(v)) c.nan_in_win += 1;
     if (c.i + 1 < W || c.nan_in_win > 0) {
       out = qnan();
     } else if (OP == FMX_TS_RANK) {
@@ -511,9 +525,9 @@ __device__ __forceinline__ void ts_set_step(SetSt& c, double v, double* ring, in
   if (Ym) __builtin_nontemporal_store(m, Ym + off);
   if (Ys) __builtin_nontemporal_store(sd, Ys + off);
   if (Yz) __builtin_nontemporal_store((v - m) / (sd == 0.0 ? qnan() : sd), Yz + off);
-  if (full && old != old) c.nan_w -= 1;
-  if (c.i >= WR && oldr != oldr) c.nan_r -= 1;
-  if (v != v) { c.nan_w += 1; c.nan_r += 1; }
+  if (full && !fin(old)) c.nan_w -= 1;
+  if (c.i >= WR && !fin(oldr)) c.nan_r -= 1;
+  if (!fin(v)) { c.nan_w += 1; c.nan_r += 1; }
   if (Yr) {
     double o = qnan();
     if (c.i + 1 >= WR && c.nan_r == 0) {
@@ -789,6 +803,7 @@ k_ts_lead_ptr(const double* __restrict__ X, double* __restrict__ Y, int64_t F, i
 //           oldest->newest fma chain as the register-ring kernel: bit-identical to it);
 //   rank:   s_t += 2*(x_p < v_t) + (x_p == v_t), so #less + (#equal + 1)/2 = (s_t + 1)/2
 //           (the same half-integer, divided by W); a NaN in the window sets a flag bit.
+// A +-inf row enters both as NaN (prep): the outputs whose window holds it are NaN.
 // p / q_t index the column's PRESENT rows (a ragged symbol's window is its last W rows):
 // the thread first walks back from its tile to the (W-1)th present row before it, then
 // forward; the lanes of a wave walk the same dates, so every row load is one coalesced
@@ -875,7 +890,7 @@ k_ts_win(const double* __restrict__ X, double* __restrict__ Y, int64_t F, int64_
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       if (!pu[k]) continue;
-      const double uk = u[k];
+      const double uk = prep(u[k]);                     // +-inf -> NaN: decay's fma chain carries it
 #pragma unroll
       for (int t = 0; t < T; ++t) {
         const double kk = pd - qW[t];                   // weight of row p in output t's window
@@ -1000,13 +1015,15 @@ k_ts_corr_rl(const double* __restrict__ X, const double* __restrict__ Ycol, doub
       const double yv = yr[q] + 0.0 * xr[q];
       const double pv = xv * yv;
       if (first) { mxy.init(pv); mx.init(xv); my.init(yv); vx.init(xv); vy.init(yv); first = false; }
-      if (i >= W) {
+      if (i >= W && pair_ok(xo[q], yo[q])) {
         const double ox = xo[q] + 0.0 * yo[q], oy = yo[q] + 0.0 * xo[q];
-        mxy.remove(ox * oy); mx.remove(ox); my.remove(oy); vx.remove(ox); vy.remove(oy);
-        cnt -= (ox + oy == ox + oy);
+        mxy.remove_ok(ox * oy); mx.remove_ok(ox); my.remove_ok(oy); vx.remove_ok(ox); vy.remove_ok(oy);
+        cnt -= 1;
       }
-      mxy.add(pv); mx.add(xv); my.add(yv); vx.add(xv); vy.add(yv);
-      cnt += (xv + yv == xv + yv);
+      if (pair_ok(xr[q], yr[q])) {
+        mxy.add_ok(pv); mx.add_ok(xv); my.add_ok(yv); vx.add_ok(xv); vy.add_ok(yv);
+        cnt += 1;
+      }
       const double cc = (double)cnt;
       const double num = (mxy.result(W) - mx.result(W) * my.result(W)) * (cc / (cc - 1.0));
       const double den = sqrt(vx.var(W, 1) * vy.var(W, 1));
@@ -1060,13 +1077,15 @@ k_ts_corr_fast(const double* __restrict__ X, const double* __restrict__ Ycol, do
       const double yv = yr[q] + 0.0 * xr[q];
       const double pv = xv * yv;
       if (first) { mxy.init(pv); sx.init(xv); sy.init(yv); first = false; }
-      if (i >= W) {
+      if (i >= W && pair_ok(xo[q], yo[q])) {
         const double ox = xo[q] + 0.0 * yo[q], oy = yo[q] + 0.0 * xo[q];
-        mxy.remove(ox * oy); sx.remove_r(ox, rt); sy.remove_r(oy, rt);
-        cnt -= (ox + oy == ox + oy);
+        mxy.remove_ok(ox * oy); sx.remove_ok_r(ox, rt); sy.remove_ok_r(oy, rt);
+        cnt -= 1;
       }
-      mxy.add(pv); sx.add_r(xv, rt); sy.add_r(yv, rt);
-      cnt += (xv + yv == xv + yv);
+      if (pair_ok(xr[q], yr[q])) {
+        mxy.add_ok(pv); sx.add_ok_r(xv, rt); sy.add_ok_r(yv, rt);
+        cnt += 1;
+      }
       const double cc = (double)cnt;
       const double ratio = cnt >= 2 ? mdiv(cc, cc - 1.0, rt[cnt - 1]) : cc / (cc - 1.0);
       const double num = (mxy.result_r(W, rt) - sx.mean_r(W, rt) * sy.mean_r(W, rt)) * ratio;
@@ -1141,13 +1160,17 @@ k_ts_corr_feat(const double* __restrict__ X, const double* __restrict__ Ycol, do
     const double pv = xv * yv;
     if (first) { mxy.init(pv); sx.init(xv); sy.init(yv); vs.init(xr); first = false; }
     if (i >= W) {
-      const double ox = xo + 0.0 * yo, oy = yo + 0.0 * xo;
-      mxy.remove(ox * oy); sx.remove_r(ox, rt); sy.remove_r(oy, rt);
-      cnt -= (ox + oy == ox + oy);
+      if (pair_ok(xo, yo)) {
+        const double ox = xo + 0.0 * yo, oy = yo + 0.0 * xo;
+        mxy.remove_ok(ox * oy); sx.remove_ok_r(ox, rt); sy.remove_ok_r(oy, rt);
+        cnt -= 1;
+      }
       vs.remove_r(xo, rt);
     }
-    mxy.add(pv); sx.add_r(xv, rt); sy.add_r(yv, rt);
-    cnt += (xv + yv == xv + yv);
+    if (pair_ok(xr, yr)) {
+      mxy.add_ok(pv); sx.add_ok_r(xv, rt); sy.add_ok_r(yv, rt);
+      cnt += 1;
+    }
     vs.add_r(xr, rt);
     const double cc = (double)cnt;
     const double ratio = cnt >= 2 ? mdiv(cc, cc - 1.0, rt[cnt - 1]) : cc / (cc - 1.0);
@@ -1187,8 +1210,9 @@ __global__ void k_ts_window0(const double* __restrict__ X, double* __restrict__ 
 
 // ------------------------------------------------------------------------------------
 // ts_corr (builder-defined; pandas Rolling.corr) on ragged panels: prep_binary NaN
-// propagation, then roll_mean(x*y), roll_mean(x), roll_mean(y), roll_sum(notna) (minp 0),
-// roll_var(x), roll_var(y) and  (mxy - mx*my) * (c/(c-1)) / sqrt(vx*vy).  The leaving
+// propagation, a pair with +-inf on either side not counted (pair_ok), then
+// roll_mean(x*y), roll_mean(x), roll_mean(y), roll_sum(notna) (minp 0), roll_var(x),
+// roll_var(y) and  (mxy - mx*my) * (c/(c-1)) / sqrt(vx*vy).  The leaving
 // pair is re-read at the trailing row pointer (k_ts_ptr), so any W; same operation order
 // as k_ts_corr_rl: bit-identical on a fully present panel.
 __global__ void __launch_bounds__(256)
@@ -1214,13 +1238,17 @@ k_ts_corr_ptr(const double* __restrict__ X, const double* __restrict__ Ycol, dou
     if (first) { mxy.init(pv); mx.init(xv); my.init(yv); vx.init(xv); vy.init(yv); first = false; tail = d; }
     if (i >= W) {
       const double txr = x[tail * ld], tyr = yc[tail * ld];
-      const double ox = txr + 0.0 * tyr, oy = tyr + 0.0 * txr;
-      mxy.remove(ox * oy); mx.remove(ox); my.remove(oy); vx.remove(ox); vy.remove(oy);
-      cnt -= (ox + oy == ox + oy);
+      if (pair_ok(txr, tyr)) {
+        const double ox = txr + 0.0 * tyr, oy = tyr + 0.0 * txr;
+        mxy.remove_ok(ox * oy); mx.remove_ok(ox); my.remove_ok(oy); vx.remove_ok(ox); vy.remove_ok(oy);
+        cnt -= 1;
+      }
       do { ++tail; } while (pres != nullptr && pres[tail * ld] == 0);
     }
-    mxy.add(pv); mx.add(xv); my.add(yv); vx.add(xv); vy.add(yv);
-    cnt += (xv + yv == xv + yv);
+    if (pair_ok(xr, yr)) {
+      mxy.add_ok(pv); mx.add_ok(xv); my.add_ok(yv); vx.add_ok(xv); vy.add_ok(yv);
+      cnt += 1;
+    }
     const double c = (double)cnt;
     const double num = (mxy.result(W) - mx.result(W) * my.result(W)) * (c / (c - 1.0));
     const double den = sqrt(vx.var(W, 1) * vy.var(W, 1));
@@ -1232,7 +1260,9 @@ k_ts_corr_ptr(const double* __restrict__ X, const double* __restrict__ Ycol, dou
 // ts_regression_fast rolling moments over the pair-valid rows of one column
 // (operations.py:204-240).  `valid` marks rows that survive the reference's dropna()
 // (y and the globally shifted x both non-NaN); output NaN elsewhere.  The leaving pair is
-// re-read at the trailing valid-row pointer: any W.
+// re-read at the trailing valid-row pointer: any W.  The reference rolls five separate
+// Series, so each of the five machines drops the +-inf of its own input alone: an x whose
+// square overflows is missing from the mean of x^2 only.
 __global__ void __launch_bounds__(256)
 k_ts_regression_ptr(const double* __restrict__ Yv, const double* __restrict__ Xv, const uint8_t* __restrict__ valid,
                     double* __restrict__ Out, int64_t D, int64_t A, int64_t ld, int W, int rettype) {

@@ -9,6 +9,12 @@ Parity: rolling sums/means/stds/zscores/ranks, shifts, cross-sectional ranks, mo
 quantile ops, group ops and regressions reproduce pandas bit-for-bit; ``ts_decay``
 (BLAS dot order) and ``log``/``power`` with general exponents agree to <= 1e-12
 relative (tests/test_gpu_parity.py).
+
+Non-finite inputs: like pandas' ``rolling``, the rolling aggregations (``ts_sum / mean / std /
+zscore / rank / decay``, ``ts_corr``, the five means of ``ts_regression_fast``) take +-inf as
+NaN -- the ``window`` windows that hold it are NaN, then the column recovers; ``ts_diff``,
+``ts_delay``, ``ts_backfill`` and ``ts_decay(window < 1)`` pass it through
+(tests/test_ts_nonfinite_host.py, tests/test_gpu_ts_paths.py).
 """
 from __future__ import annotations
 

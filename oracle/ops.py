@@ -53,27 +53,35 @@ def _mask_out(out, present):
     return out
 
 
+def _prep(c):
+    """What a rolling aggregation sees: pandas ``Rolling._prep_values`` replaces +-inf by NaN
+    before sum / mean / std / apply / corr, so one inf empties the ``window`` windows that
+    hold it and the column then recovers.  The shift operators (diff, delay, backfill, and
+    decay with window < 1) are not aggregations and keep +-inf."""
+    return np.where(np.isinf(c), np.nan, c)
+
+
 # --------------------------------------------------------------------------- time series
 def ts_sum(x, window, present=None):
     """operations.py:6-7 -- rolling(window).sum() per symbol."""
-    return _ts(x, present, lambda c: nm.roll_sum(c, window))
+    return _ts(x, present, lambda c: nm.roll_sum(_prep(c), window))
 
 
 def ts_mean(x, window, present=None):
     """operations.py:10-11 -- rolling(window).mean() per symbol."""
-    return _ts(x, present, lambda c: nm.roll_mean(c, window))
+    return _ts(x, present, lambda c: nm.roll_mean(_prep(c), window))
 
 
 def ts_std(x, window, present=None):
     """operations.py:14-15 -- rolling(window).std() (ddof=1, zsqrt)."""
-    return _ts(x, present, lambda c: nm.zsqrt(nm.roll_var(c, window, 1)))
+    return _ts(x, present, lambda c: nm.zsqrt(nm.roll_var(_prep(c), window, 1)))
 
 
 def ts_zscore(x, window, present=None):
-    """operations.py:18-21 -- (x - mean) / std.replace(0, nan)."""
+    """operations.py:18-21 -- (x - mean) / std.replace(0, nan); the numerator keeps the raw x."""
     def f(c):
-        m = nm.roll_mean(c, window)
-        s = nm.zsqrt(nm.roll_var(c, window, 1))
+        m = nm.roll_mean(_prep(c), window)
+        s = nm.zsqrt(nm.roll_var(_prep(c), window, 1))
         s = np.where(s == 0, np.nan, s)
         with np.errstate(all="ignore"):
             return (c - m) / s
@@ -82,8 +90,9 @@ def ts_zscore(x, window, present=None):
 
 def ts_rank(x, window, present=None):
     """operations.py:23-32 -- pct rank (average ties) of the last element of each full
-    window: (#less + (#equal + 1) / 2) / window; NaN anywhere in the window -> NaN."""
+    window: (#less + (#equal + 1) / 2) / window; NaN or +-inf anywhere in the window -> NaN."""
     def f(c):
+        c = _prep(c)
         T = c.shape[0]
         out = np.full(c.shape, np.nan)
         for i in range(window - 1, T):
@@ -126,7 +135,8 @@ def ts_delay(x, window, present=None):
 
 def ts_decay(x, window, present=None):
     """operations.py:40-48 -- linearly weighted moving average, weights 1..window
-    (newest heaviest), min_periods=window; window < 1 returns the input."""
+    (newest heaviest), min_periods=window, NaN or +-inf anywhere in the window -> NaN;
+    window < 1 returns the input (+-inf included)."""
     x = np.asarray(x, dtype=np.float64)
     if window < 1:
         return x.copy() if present is None else _mask_out(x.copy(), present)
@@ -134,6 +144,7 @@ def ts_decay(x, window, present=None):
     den = float(np.arange(1, window + 1).sum())
 
     def f(c):
+        c = _prep(c)
         T = c.shape[0]
         out = np.full(c.shape, np.nan)
         for i in range(window - 1, T):
@@ -157,12 +168,15 @@ def ts_backfill(x, present=None):
 def ts_corr(x, y, window, present=None):
     """Builder-defined (no reference counterpart; pinned to pandas, not the reference):
     per-symbol ``x.rolling(window).corr(y)``.  pandas ``Rolling.corr`` = prep_binary NaN
-    propagation, then (mean(xy) - mean(x) mean(y)) * (c / (c - 1)) / sqrt(var(x) var(y))
-    with roll_mean / roll_sum(notna, minp=0) / roll_var (ddof=1)."""
+    propagation, +-inf in either side to NaN, then
+    (mean(xy) - mean(x) mean(y)) * (c / (c - 1)) / sqrt(var(x) var(y))
+    with roll_mean / roll_sum(notna, minp=0) / roll_var (ddof=1).  The product is of the
+    prepped pair and is not prepped again: where x * y itself overflows pandas' result is an
+    accident of its implementation and is not pinned (DESIGN "Rolling kernels")."""
     def f(cx, cy):
         with np.errstate(all="ignore"):
-            xv = cx + 0 * cy
-            yv = cy + 0 * cx
+            xv = _prep(cx + 0 * cy)
+            yv = _prep(cy + 0 * cx)
             mxy = nm.roll_mean(xv * yv, window)
             mx = nm.roll_mean(xv, window)
             my = nm.roll_mean(yv, window)
@@ -402,7 +416,9 @@ def ts_regression_fast_long(dcode, scode, y, x, window, lag=0, rettype=2):
     """operations.py:185-246 on long arrays in input row order.
 
     ``x.shift(lag)`` is a global row shift (crosses symbols), rows with NaN y or x are
-    dropped, rolling means run per symbol over the remaining rows, NaN results are
+    dropped (+-inf rows stay), rolling means run per symbol over the remaining rows -- five
+    separate Series, each with its own +-inf replaced by NaN, so an x whose square overflows
+    is missing from the mean of x^2 only --, NaN results are
     dropped and the output is sorted by (date, symbol).  Returns (d, s, v).
     """
     if rettype not in (0, 1, 2, 3, 6):
@@ -421,18 +437,18 @@ def ts_regression_fast_long(dcode, scode, y, x, window, lag=0, rettype=2):
     for sym in np.unique(scode[ok]):
         rows = np.nonzero(ok & (scode == sym))[0]
         gx, gy = xs[rows], y[rows]
-        mx = nm.roll_mean(gx, window)
-        my = nm.roll_mean(gy, window)
-        ex2 = nm.roll_mean(gx ** 2, window)
-        exy = nm.roll_mean(gx * gy, window)
         with np.errstate(all="ignore"):
+            mx = nm.roll_mean(_prep(gx), window)
+            my = nm.roll_mean(_prep(gy), window)
+            ex2 = nm.roll_mean(_prep(gx ** 2), window)
+            exy = nm.roll_mean(_prep(gx * gy), window)
             cov = exy - mx * my
             var_x = ex2 - mx ** 2
             beta = cov / var_x
             alpha = my - beta * mx
             fitted = alpha + beta * gx
             resid = gy - fitted
-            var_y = nm.roll_mean(gy ** 2, window) - my ** 2
+            var_y = nm.roll_mean(_prep(gy ** 2), window) - my ** 2
             r2 = cov ** 2 / (var_x * var_y)
         v = {0: resid, 1: alpha, 2: beta, 3: fitted, 6: r2}[rettype]
         keep = ~np.isnan(v)
