@@ -126,6 +126,10 @@ SIGNATURES = {
                    c_vp, c_vp],
     "fmx_ts_ols": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
                    c_vp, c_vp, c_vp, c_vp],
+    "fmx_risk_books": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "fmx_risk_mvo_books": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl, c_i32, c_dbl, c_vp,
+                           c_vp, c_vp, c_vp],
+    "fmx_risk_mvo_books_work_bytes": [c_i64, c_i64, c_i64],
 }
 _RESTYPES = {"fmx_last_error": c_cp, "fmx_build_variant": c_cp, "fmx_ic_ranked_work_len": c_i64, "fmx_rank_ic_work_len": c_i64, "fmx_gram_work_bytes": c_i64, "fmx_gram_direct_work_bytes": c_i64,
              "fmx_gram_direct_exact_work_bytes": c_i64, "fmx_ic_daily_sorted_work_bytes": c_i64,
@@ -135,7 +139,7 @@ _RESTYPES = {"fmx_last_error": c_cp, "fmx_build_variant": c_cp, "fmx_ic_ranked_w
              "fmx_gram_exact_rows_work_bytes": c_i64,
              "fmx_mvo_windows_work_bytes": c_i64, "fmx_sim_mvo_books_work_bytes": c_i64,
              "fmx_sim_mvo_turnover_books_work_bytes": c_i64, "fmx_sim_mvo_turnover_chains_work_bytes": c_i64,
-             "fmx_sim_mvo_window_rows_work_bytes": c_i64,
+             "fmx_sim_mvo_window_rows_work_bytes": c_i64, "fmx_risk_mvo_books_work_bytes": c_i64,
              "fmx_debug_exact_fold": None}
 
 # constants mirrored from include/fmx.h

@@ -1176,6 +1176,82 @@ def sim_mvo_books(R0, win_rows, win_T, X, present=None, shrinkage=0.1, max_weigh
     return W, counts, info
 
 
+RISK_MAX_K = 32             # fmx_risk_books / fmx_risk_mvo_books: the K x K matrices live in LDS (fmx_cs_ols' cap)
+
+
+def _check_risk_model(fn, B, Fc, S2):
+    """(K, D, A) of the factor model's three device arrays B [K][D][A], Fc [D][K][K], S2 [D][A]."""
+    for t, name, nd in ((B, "B", 3), (Fc, "Fc", 3), (S2, "S2", 2)):
+        if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != F64 or t.dim() != nd
+                or not t.is_contiguous()):
+            raise _lib.FmxError(f"{fn}: {name} must be a contiguous float64 {nd}-D HIP device tensor")
+    K, D, A = B.shape
+    if not 1 <= K <= RISK_MAX_K:
+        raise _lib.FmxError(f"{fn}: K = {K} factors; the kernel takes 1..{RISK_MAX_K}")
+    if tuple(Fc.shape) != (D, K, K) or tuple(S2.shape) != (D, A):
+        raise _lib.FmxError(f"{fn}: B is {tuple(B.shape)}, so Fc must be [{D}][{K}][{K}] and S2 [{D}][{A}]")
+    return K, D, A
+
+
+def risk_books(B, Fc, S2, W, present=None, valid=None, marginal=False):
+    """Predicted risk and attribution of M books under Sigma_d = B_d' F_d B_d + diag(s2_d)
+    (fmx_risk_books): B [K][D][A] exposures (NaN: 0), Fc [D][K][K] (lower triangle),
+    S2 [D][A], W [M][D][A] (or [D][A]) books (NaN: not held), present [D][A] uint8 or None, valid
+    [D] uint8 / bool or None (an invalid date is NaN everywhere).  Returns a dict: var [M][D][3]
+    (total, factor, specific), expo [M][D][K], contrib [M][D][K] and, with ``marginal``, marginal
+    [M][D][A] = Sigma w (NaN on absent cells)."""
+    K, D, A = _check_risk_model("risk_books", B, Fc, S2)
+    if not isinstance(W, torch.Tensor) or W.device != B.device or W.dtype != F64 or W.dim() not in (2, 3):
+        raise _lib.FmxError("risk_books: W must be a float64 [M][D][A] tensor on B's device")
+    W = as3(W).contiguous()
+    M = W.shape[0]
+    if tuple(W.shape[1:]) != (D, A):
+        raise _lib.FmxError(f"risk_books: W is {tuple(W.shape)}, expected [M][{D}][{A}]")
+    _check_present(present, D, A)
+    if valid is not None:
+        valid = torch.as_tensor(valid).to(device=B.device, dtype=torch.uint8).contiguous()
+        if tuple(valid.shape) != (D,):
+            raise _lib.FmxError(f"risk_books: valid must be [{D}]")
+    dev = B.device
+    out = {"var": torch.empty((M, D, 3), dtype=F64, device=dev), "expo": torch.empty((M, D, K), dtype=F64, device=dev),
+           "contrib": torch.empty((M, D, K), dtype=F64, device=dev)}
+    if marginal:
+        out["marginal"] = torch.empty((M, D, A), dtype=F64, device=dev)
+    call("fmx_risk_books", ptr(B), ptr(Fc), ptr(S2), ptr(W), ptr(present), ptr(valid), int(K), int(D), int(A), int(M),
+         ptr(out["var"]), ptr(out["expo"]), ptr(out["contrib"]), ptr(out.get("marginal")), stream_ptr())
+    return out
+
+
+def risk_mvo_books(B, Fc, S2, X, present=None, model_row=None, max_weight=0.03, max_iter=20000, eps=1e-9):
+    """``sim_mvo_books``' QP against the factor model (fmx_risk_mvo_books): book j is
+    the minimum-variance long/short book of signal X[j] under diag(S2[r]) + B[:, r]' Fc[r] B[:, r],
+    r = model_row[j] (default: j, for a model with one date per book; -1: no model, status 4).
+    B [K][Dm][A], Fc [Dm][K][K], S2 [Dm][A], X [J][A], present [J][A] uint8 or None.  Returns
+    (W [J][A], counts [J][2], info [J][6]) as ``sim_mvo_books`` (info[:, 4] = the smallest
+    specific variance of the active cells).  A model_row outside [-1, Dm) raises FmxError."""
+    K, Dm, A = _check_risk_model("risk_mvo_books", B, Fc, S2)
+    if not isinstance(X, torch.Tensor) or X.device != B.device or X.dtype != F64 or X.dim() != 2:
+        raise _lib.FmxError("risk_mvo_books: X must be a float64 [J][A] tensor on B's device")
+    X = X.contiguous()
+    J = X.shape[0]
+    if X.shape[1] != A or not 1 <= A <= SIM_MVO_MAX_A:
+        raise _lib.FmxError(f"risk_mvo_books: B and X must share 1 <= A <= {SIM_MVO_MAX_A} asset columns")
+    _check_present(present, J, A)
+    if model_row is None:
+        if J != Dm:
+            raise _lib.FmxError(f"risk_mvo_books: model_row is needed when X has {J} rows and the model {Dm} dates")
+        model_row = torch.arange(J, dtype=torch.int32)
+    model_row = torch.as_tensor(model_row, dtype=torch.int32).to(X.device).contiguous()
+    if tuple(model_row.shape) != (J,):
+        raise _lib.FmxError(f"risk_mvo_books: model_row must be [{J}]")
+    W = torch.empty((J, A), dtype=F64, device=X.device)
+    counts = torch.empty((J, 2), dtype=F64, device=X.device)
+    info = torch.empty((J, 6), dtype=F64, device=X.device)
+    call("fmx_risk_mvo_books", ptr(B), ptr(Fc), ptr(S2), int(K), int(Dm), int(A), ptr(model_row), ptr(X), ptr(present),
+         int(J), float(max_weight), int(max_iter), float(eps), ptr(W), ptr(counts), ptr(info), stream_ptr())
+    return W, counts, info
+
+
 def sim_mvo_turnover_books(R0, win_rows, win_T, X, present=None, W=None, shrinkage=0.1, max_weight=0.03,
                            turnover_penalty=0.1, return_weight=0.0, max_iter=20000, eps=1e-9, return_opt=False):
     """Simulation._daily_trade_list, method 'mvo_turnover' (portfolio_simulation.py:206-248,

@@ -108,6 +108,9 @@ def compute_multimanager_weights(factors_df: pd.DataFrame, factor_weights: pd.Da
             mgrs.append(fac)
     if mgrs and method not in ("equal", "linear") + HOST_METHODS:
         raise ValueError(f"Unknown method {method}")
+    if method in HOST_METHODS and _setting(settings, "risk_model", None) is not None:
+        raise ValueError("risk_model: the multi-manager MVO books against a factor risk model are out of scope; "
+                         "run Simulation(method='mvo', risk_model=...) per manager")
     all_symbols = factors_df.index.get_level_values("symbol").unique()
     if len(factor_weights.index) == 0:
         return pd.Series(dtype=float), pd.DataFrame(columns=["long_count", "short_count"])

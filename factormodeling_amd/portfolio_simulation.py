@@ -44,7 +44,7 @@ from . import _refload
 from . import engine as E
 from .panel import device
 from .simulation import (daily_trade_list, mvo_runs_natively, mvo_trade_list, mvo_turnover_runs_natively,
-                         mvo_turnover_trade_list)
+                         mvo_turnover_trade_list, risk_mvo_runs_natively, risk_mvo_trade_list)
 
 RESULT_COLS = ["log_return", "long_return", "short_return", "long_turnover", "short_turnover", "turnover"]
 
@@ -73,6 +73,8 @@ class SimulationSettings:
     shrinkage_intensity: float = 0.1
     turnover_penalty: float = 0.1
     return_weight: float = 0.0
+    # builder-defined: a fitted risk_model.FactorRiskModel; method 'mvo' then optimises against it
+    risk_model: object = None
 
 
 def reference_simulation_classes():
@@ -144,6 +146,7 @@ class Simulation:
         self.shrinkage_intensity = s.shrinkage_intensity
         self.turnover_penalty = s.turnover_penalty
         self.return_weight = s.return_weight
+        self.risk_model = getattr(s, "risk_model", None)
 
     def run(self):
         """portfolio_simulation.py:73-95."""
@@ -171,6 +174,8 @@ class Simulation:
     # ----------------------------------------------------------------------------- trade list
     def _daily_trade_list(self):
         """portfolio_simulation.py:96-154 (equal / linear / mvo on the device)."""
+        if self.risk_model is not None and self.method in ("mvo", "mvo_turnover"):
+            return self._risk_model_trade_list()
         if self.method == "mvo" and self._mvo_runs_natively():
             return self._native_mvo_trade_list()
         if self.method == "mvo_turnover" and self._mvo_turnover_runs_natively():
@@ -228,6 +233,25 @@ class Simulation:
             logging.getLogger("portfolio_simulation").warning(
                 "mvo: of %d days, %d stopped at the iteration limit (last iterate kept) and %d took the "
                 "equal-leg fallback x0 (one-row window or max_weight too small for a leg)", len(info), n1, n2)
+        return shifted, counts
+
+    def _risk_model_trade_list(self):
+        """'mvo' against ``settings.risk_model`` (``simulation.risk_mvo_trade_list``; DESIGN §26);
+        days the solver left unconverged or answered with the x0 fallback are reported once."""
+        if self.method != "mvo":
+            raise ValueError("risk_model: method 'mvo_turnover' against a factor risk model is out of scope; "
+                             "use method='mvo'")
+        if not risk_mvo_runs_natively(self.custom_feature, self.risk_model, self.use_cvxpy):
+            raise ValueError("risk_model: method 'mvo' against a factor risk model runs on the device only (a GPU, "
+                             "use_cvxpy=True, a unique (date, symbol) Series, at most 32 factors and 16,384 symbols)")
+        shifted, counts, extra = risk_mvo_trade_list(self.custom_feature, self.risk_model, self.pct, self.max_weight,
+                                                     return_info=True)
+        info = extra["info"]
+        n1, n2 = int((info[:, 0] == 1).sum()), int((info[:, 0] == 2).sum())
+        if n1 or n2:
+            logging.getLogger("portfolio_simulation").warning(
+                "mvo: of %d days, %d stopped at the iteration limit (last iterate kept) and %d took the "
+                "equal-leg fallback x0 (max_weight too small for a leg or an unusable risk model row)", len(info), n1, n2)
         return shifted, counts
 
     def _host_trade_list(self):

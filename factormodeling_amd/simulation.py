@@ -24,6 +24,10 @@ managers of ``multi_manager.compute_multimanager_weights`` in one device pass: m
 ``factors_df[cols[f]].dropna()``, with its own windows (``engine.sim_mvo_window_rows``) and, for
 'mvo_turnover', its own date list (``engine.sim_mvo_turnover_chains``, one chain per manager).
 
+``risk_mvo_trade_list(custom_feature, model, ...)`` is ``mvo_trade_list`` against a fitted
+``risk_model.FactorRiskModel`` (Sigma = B'F B + diag(s2) of each date) instead of the returns
+window: ``k_risk_mvo`` (csrc/sim_mvo_risk.hip), one launch for all dates.
+
 ``mvo_runs_natively`` / ``mvo_turnover_runs_natively`` are the conditions under which the MVO
 methods run on the device, shared by ``Simulation`` and ``multi_manager``.
 """
@@ -227,7 +231,67 @@ def mvo_trade_list(custom_feature: pd.Series, returns: pd.Series, pct: float = 0
     return shifted, counts_df
 
 
+def risk_mvo_trade_list(custom_feature: pd.Series, model, pct: float = 0.1, max_weight: float = 0.03,
+                        return_info: bool = False, max_iter: int = 20000, eps: float = 1e-9):
+    """``mvo_trade_list`` against a fitted ``risk_model.FactorRiskModel`` instead of the returns
+    window: every date's book minimises w'Sigma w under the model's Sigma of that date
+    (engine.risk_mvo_books), with the constraints, statuses and the
+    ``(shifted, counts_df[, extra])`` result of ``mvo_trade_list``.  A date the model does not
+    have, or has as invalid, carries the equal-weight book (status 4).  The feature's symbols
+    must be symbols of the model."""
+    custom_feature = by_date(custom_feature)
+    dev = device()
+    pi = panel_index(custom_feature.index)
+    mp = model.panel_index
+    scol = mp.symbols.get_indexer(pi.symbols)
+    if (scol < 0).any():
+        raise ValueError("risk_mvo_trade_list: the feature has symbols the risk model does not")
+    cols = scol[pi.s]
+    xh = np.full((pi.D, mp.A), np.nan)
+    xh[pi.d, cols] = custom_feature.to_numpy(dtype=np.float64)
+    ph = np.zeros((pi.D, mp.A), dtype=np.uint8)
+    ph[pi.d, cols] = 1
+    mrow = mp.dates.get_indexer(pi.dates).astype(np.int32)
+    ok = model.valid.to_numpy()
+    mrow[mrow >= 0] = np.where(ok[mrow[mrow >= 0]], mrow[mrow >= 0], -1)
+    X, present = torch.as_tensor(xh, device=dev), torch.as_tensor(ph, device=dev)
+    W, counts, info = E.risk_mvo_books(model.B, model.Fc, model.S2, X, present, mrow, max_weight, max_iter, eps)
+    eq = info[:, 0] == 4
+    if bool(eq.any()):
+        _, ce, we = E.trade_books(X[None], "equal", pct, max_weight, present=present, nan_absent=False, raw=True)
+        W[eq] = we[0][eq]
+        counts[eq] = ce[0][eq]
+    Ws = E.shift_rows(W)[0].cpu().numpy()
+    order = np.argsort(pi.flat)
+    d, s = pi.d[order], pi.s[order]
+    index = pd.MultiIndex.from_arrays([pi.dates[d], pi.symbols[s]], names=list(custom_feature.index.names))
+    shifted = pd.Series(Ws[d, scol[s]], index=index)
+    cn = counts.cpu().numpy()
+    counts_df = pd.DataFrame({"long_count": cn[:, 0].astype(np.int64), "short_count": cn[:, 1].astype(np.int64)},
+                             index=pd.Index(pi.dates, name=custom_feature.index.names[0]))
+    if return_info:
+        return shifted, counts_df, {"info": info.cpu().numpy(), "books": W.cpu().numpy()[:, scol], "dates": pi.dates,
+                                    "symbols": pi.symbols}
+    return shifted, counts_df
+
+
 # ----------------------------------------------------------------------------- routing
+def risk_mvo_runs_natively(feature, model, use_cvxpy) -> bool:
+    """'mvo' against a factor risk model runs on the device under ``mvo_runs_natively``'s
+    conditions without the lookback and shrinkage caps (the model replaces the window), with
+    at most 32 factors."""
+    if not use_cvxpy or os.environ.get("FMX_SIM_MVO", "").lower() == "reference":
+        return False
+    if not torch.cuda.is_available() or not isinstance(feature, pd.Series):
+        return False
+    idx = feature.index
+    if not isinstance(idx, pd.MultiIndex) or idx.nlevels != 2 or not idx.is_unique:
+        return False
+    if not 1 <= getattr(model, "K", 0) <= E.RISK_MAX_K:
+        return False
+    return model.panel_index.A <= E.SIM_MVO_MAX_A
+
+
 def mvo_runs_natively(feature, returns, use_cvxpy, lookback_period, shrinkage_intensity) -> bool:
     """'mvo' solves every date's QP on the device unless the caller asked for the host SLSQP
     solver (``use_cvxpy=False``) or the reference (``FMX_SIM_MVO=reference``), no GPU is

@@ -646,6 +646,40 @@ fmx_status fmx_sim_mvo_window_rows(const uint8_t* fpresent, const uint8_t* rpres
                                    int64_t N, int64_t A, int64_t Dr, int64_t Lmax, int32_t* win_rows, int32_t* win_T,
                                    void* work, int64_t work_bytes, void* stream);
 
+/* ---- factor risk model (builder-defined) ------------------------------- */
+/* Sigma_d = B_d' F_d B_d + diag(s2_d) over the symbols present on date d: B [K][D][A] the
+ * exposures (a non-finite exposure and an absent symbol count as 0), Fc [D][K][K] the factor
+ * covariance (the lower triangle is read), S2 [D][A] the specific variances, 1 <= K <= 32.
+ * Predicted risk and attribution of M books W [M][D][A] (a NaN cell is not held: 0)
+ * (csrc/risk_model.hip):
+ *   var [M][D][3] = (total, factor = b'F b with b = B w, specific = sum w^2 s2);
+ *   expo [M][D][K] = b;  contrib [M][D][K] = b_k (F b)_k (their sum over k is the factor variance);
+ *   marginal [M][D][A] or NULL = (Sigma w)_a = sum_k B_ka (F b)_k + s2_a w_a, NaN on absent cells.
+ * present [D][A] or NULL (every cell is a row); valid [D] (uint8) or NULL: a date with
+ * valid[d] == 0 is NaN in every output.  Every sum runs in a fixed order that depends on
+ * neither M nor D: a book has the same bits alone or in a batch, a date alone or in a panel.
+ * The exposures of a date are read once per 16 books (once more for marginal). */
+fmx_status fmx_risk_books(const double* B, const double* Fc, const double* S2, const double* W, const uint8_t* present,
+                          const uint8_t* valid, int64_t K, int64_t D, int64_t A, int64_t M, double* var, double* expo,
+                          double* contrib, double* marginal, void* stream);
+/* fmx_sim_mvo_books' QP -- the same constraints, box, counts, info [J][6] and status codes --
+ * against the factor model (csrc/sim_mvo_risk.hip): book j is optimised under
+ * Sigma = diag(S2[r]) + B[.][r]' Fc[r] B[.][r] on its active cells, r = model_row[j].
+ *   B [K][Dm][A], Fc [Dm][K][K], S2 [Dm][A]: the model's Dm dates, 1 <= K <= 32, A <= 16384;
+ *   model_row [J] (device int32): -1 = no model for book j -> status 4 (zeros, counts 0; the
+ *     caller supplies the equal-weight book).  Read back and checked before the launch: an
+ *     entry outside [-1, Dm) is FMX_ERR_ARG;
+ *   X [J][A] the signal, present [J][A] or NULL.
+ * ADMM with a Woodbury x-step over a per-asset diagonal and a K x K core.  status 2 (x0)
+ * also covers a non-finite or negative S2 on an active cell, a non-finite Fc entry and an Fc
+ * that is not positive semidefinite.  info[4] = min S2 over the active cells, info[5] = rho.
+ * The K x K matrices live in LDS: fmx_risk_mvo_books_work_bytes is 0 and no workspace is taken. */
+int64_t fmx_risk_mvo_books_work_bytes(int64_t A, int64_t K, int64_t J);
+fmx_status fmx_risk_mvo_books(const double* B, const double* Fc, const double* S2, int64_t K, int64_t Dm, int64_t A,
+                              const int32_t* model_row, const double* X, const uint8_t* present, int64_t J,
+                              double max_weight, int32_t max_iter, double eps, double* W, double* counts, double* info,
+                              void* stream);
+
 /* ---- portfolio P&L (portfolio_simulation.py:748-819) ---------- */
 /* Replaces Simulation._daily_portfolio_returns' per-date sums on the aligned [D][A] grid
  * (union of the weights' and returns' dates/symbols; NaN cells count as 0 as after
