@@ -20,7 +20,7 @@
 // sum has one fixed order (a lane's assets ascending, the xor-shuffle tree, then k or j
 // ascending), which does not depend on M, D or the tile: a book gives the same bits alone or
 // in a batch, a date the same bits alone or inside a panel.  Plain fp64 with fma; no atomics.
-#include "fmx_common.hpp"
+#include "sim_mvo_common.hpp"   // smv_finite, smv_wsum
 
 namespace fmx {
 namespace {
@@ -29,14 +29,6 @@ constexpr int RB_NT = 1024;      // 16 waves: one per pair of factor rows at K =
 constexpr int RB_MAX_K = 32;
 constexpr int RB_TILE = 16;      // books per workgroup
 constexpr int RB_CA = 256;       // assets per staged chunk
-
-__device__ __forceinline__ bool rb_finite(double v) {
-  return (((uint32_t)__double2hiint(v) >> 20) & 0x7ffu) != 0x7ffu;
-}
-__device__ __forceinline__ double rb_wsum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 template <int MT>
 __global__ __launch_bounds__(RB_NT) void k_risk_books(const double* __restrict__ B, const double* __restrict__ Fc,
@@ -96,8 +88,8 @@ __global__ __launch_bounds__(RB_NT) void k_risk_books(const double* __restrict__
     if (rows) {
       for (int c = lane; c < cn; c += 64) {
         double b0 = r0[c0 + c], b1 = r1[c0 + c];
-        b0 = rb_finite(b0) ? b0 : 0.0;
-        b1 = two && rb_finite(b1) ? b1 : 0.0;
+        b0 = smv_finite(b0) ? b0 : 0.0;
+        b1 = two && smv_finite(b1) ? b1 : 0.0;
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
           if (m < mt) {
@@ -119,7 +111,7 @@ __global__ __launch_bounds__(RB_NT) void k_risk_books(const double* __restrict__
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       if (m < mt) {
-        const double s0 = rb_wsum(a0[m]), s1 = rb_wsum(a1[m]);
+        const double s0 = smv_wsum(a0[m]), s1 = smv_wsum(a1[m]);
         if (lane == 0) {
           bl[m][k0] = s0;
           if (two) bl[m][k0 + 1] = s1;
@@ -128,7 +120,7 @@ __global__ __launch_bounds__(RB_NT) void k_risk_books(const double* __restrict__
     }
   }
   if (wv < mt) {
-    as = rb_wsum(as);
+    as = smv_wsum(as);
     if (lane == 0) sv[wv] = as;
   }
   __syncthreads();
@@ -164,7 +156,7 @@ __global__ __launch_bounds__(RB_NT) void k_risk_books(const double* __restrict__
     if (pr) {
       for (int k = 0; k < K; ++k) {
         double b = B[(int64_t)k * DA + d * A + a];
-        b = rb_finite(b) ? b : 0.0;
+        b = smv_finite(b) ? b : 0.0;
 #pragma unroll
         for (int m = 0; m < MT; ++m)
           if (m < mt) acc[m] = __builtin_fma(b, fb[m][k], acc[m]);

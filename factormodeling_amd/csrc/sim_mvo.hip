@@ -30,12 +30,9 @@
 // The centred Gram is M^-1's source: C C' = sum over active columns, one staged row at a time.
 // All arithmetic is plain fp64 (fma); no fast-math, no cooperative launch, <= 16 waves.
 //
-// The phases (legs, window statistics, Gram, power iteration, sweep, Woodbury apply) are the
-// functions of sim_mvo_common.hpp, shared with sim_mvo_turnover.hip.
+// Every phase is a function of sim_mvo_common.hpp; this file is their sequence and the entry point.
 //
 // Caps: A <= 16,384 (SMV_MAX_A), T <= 64 rows per window (SMV_MAX_T).
-#include <vector>
-
 #include "sim_mvo_common.hpp"
 
 namespace fmx {
@@ -51,158 +48,46 @@ __global__ __launch_bounds__(1024) void k_sim_mvo(const double* __restrict__ R0,
                                                   double* __restrict__ W, double* __restrict__ counts,
                                                   double* __restrict__ info, double* __restrict__ work) {
   extern __shared__ double sm[];
-  double* vec = sm;                          // [A]
-  double* gv = vec + A;                      // [SMV_MAX_T]
-  double* hv = gv + SMV_MAX_T;               // [SMV_MAX_T]
-  double* red = hv + SMV_MAX_T;              // [2 * SMV_RED]
-  int* rows = (int*)(red + 2 * SMV_RED);     // [SMV_MAX_T]
+  const SmvLds l = smv_carve(sm, A);
   const int64_t j = blockIdx.x;
-  double* M = work ? work + j * (SMV_MAX_T * SMV_MAX_T) : sm + A + SMV_SMALL;   // [T * T]
-  const int tid = threadIdx.x, NT = blockDim.x;
   const int T = win_T[j];
-  const double* xj = X + j * A;
-  const uint8_t* pj = present ? present + j * A : nullptr;
   double* wj = W + j * A;
-  double* inf = info + j * 6;
-  SmvDay d = {R0, A, T, rows, vec, gv, hv, red, M, 0};
-  int& buf = d.buf;
+  double* M = work ? work + j * (SMV_MAX_T * SMV_MAX_T) : l.tail;   // [T * T]
+  SmvDay d = {R0, A, T, l.rows, l.vec, l.gv, l.hv, l.red, M, 0};
 
   // ---- the day's legs
   int sg[EPT];      // +1 / -1 on the legs, 0 elsewhere
   bool pr[EPT];     // the symbol has a row on this date
-  double cp, cn, cr;
-  smv_signs<EPT>(xj, pj, A, sg, pr, cp, cn, cr);
-  smv_sum3(red, buf, cp, cn, cr);
-  const double npos = cp, nneg = cn, npres = cr;
-
+  double npos, nneg, npres;
+  smv_signs<EPT>(X + j * A, present ? present + j * A : nullptr, A, sg, pr, npos, nneg, npres);
+  smv_sum3(d.red, d.buf, npos, nneg, npres);
   const bool flat = npos == 0.0 || nneg == 0.0 || npres < 2.0;
   const bool feasible = u * npos >= 1.0 - 1e-12 && u * nneg >= 1.0 - 1e-12;
+  double m[EPT], delta = 0.0, sc2 = 0.0, rho = 0.0;
+  int st = flat ? 3 : (T == 0 ? 4 : 2);
+  // no solve today: a zero row, or x0 on status 2.  The test names T itself: the set-up's loops
+  // and divisions are compiled knowing T >= 2
   if (flat || T <= 1 || !feasible) {
-    const bool x0 = !flat && T != 0;
-    const double wl = x0 ? 1.0 / npos : 0.0, ws = x0 ? -1.0 / nneg : 0.0;
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      const int a = tid + e * NT;
-      if (a < A) wj[a] = pr[e] ? (sg[e] > 0 ? wl : (sg[e] < 0 ? ws : 0.0)) : qnan();
-    }
-    if (tid == 0) {
-      counts[2 * j] = x0 ? npos : 0.0;
-      counts[2 * j + 1] = x0 ? nneg : 0.0;
-      inf[0] = flat ? 3.0 : (T == 0 ? 4.0 : 2.0);
-      inf[1] = inf[2] = inf[3] = inf[4] = inf[5] = 0.0;
-    }
+    const bool x0 = st == 2;
+    smv_write_row<EPT>(wj, A, sg, pr, x0 ? 1.0 / npos : 0.0, x0 ? -1.0 / nneg : 0.0);
+    smv_write_info(counts + 2 * j, info + 6 * j, x0 ? npos : 0.0, x0 ? nneg : 0.0, st, 0, 0.0, 0.0, 0.0, 0.0);
     return;
   }
-
-  // ---- column means and the diagonal of the sample covariance
-  if (tid < T) rows[tid] = win_rows[j * Lmax + tid];
-  __syncthreads();
-  double m[EPT];
-  smv_col_means<EPT>(d, m);
-  double dsum = smv_diag_sum<EPT>(d, m, pr);
-  dsum = smv_sum(red, buf, dsum);
-  const double avg_var = dsum / ((double)(T - 1) * npres) + 1e-6;
-  const double q = shrink > 0.0 ? 1.0 - shrink : 1.0;
-  const double delta = q * 1e-6 + (shrink > 0.0 ? shrink * avg_var : 0.0);
-  const double sc2 = q / (double)(T - 1);
-
-  // ---- centred Gram over the active columns, its l_max, rho
-  smv_gram<EPT>(d, m, sg);
-  const double rho = smv_rho(delta, sc2, smv_lmax(d));
-  const double c = 2.0 * delta + rho;
-
-  // ---- M = c/2 I + sc2 G, inverted in place
-  const int TT = T * T;
-  if (smv_sweep(d, c, sc2, rho)) {   // a non-finite return in the window: the solver has no answer, x0 (:451-459)
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      const int a = tid + e * NT;
-      if (a < A) wj[a] = pr[e] ? (sg[e] > 0 ? 1.0 / npos : (sg[e] < 0 ? -1.0 / nneg : 0.0)) : qnan();
-    }
-    if (tid == 0) {
-      counts[2 * j] = npos;
-      counts[2 * j + 1] = nneg;
-      inf[0] = 2.0;
-      inf[1] = inf[2] = inf[3] = 0.0;
-      inf[4] = delta;
-      inf[5] = rho;
-    }
+  if (smv_window_setup<EPT>(d, win_rows + j * Lmax, sg, pr, npres, shrink, m, delta, sc2, rho)) {
+    smv_write_row<EPT>(wj, A, sg, pr, 1.0 / npos, -1.0 / nneg);
+    smv_write_info(counts + 2 * j, info + 6 * j, npos, nneg, 2, 0, 0.0, 0.0, delta, rho);
     return;
   }
-  for (int idx = tid; idx < TT; idx += NT) M[idx] = -M[idx];
-  __syncthreads();
+  __syncthreads();   // M^-1 is complete
 
-  // ---- p+ = K^-1 e+, p- = K^-1 e-, and the 2 x 2 system of the leg multipliers
-  double pp[EPT], pn[EPT];
-  const double rc = 1.0 / c;
-  double t1, t2, a11, a12, a22;
-  smv_leg_system<EPT>(d, pp, pn, m, sg, sc2, rc, a11, a12, a22);
-  const double rdet = 1.0 / (a11 * a22 - a12 * a12);
-
-  // ---- ADMM from x0
-  double z[EPT], y[EPT];
-#pragma unroll
-  for (int e = 0; e < EPT; ++e) {
-    z[e] = sg[e] > 0 ? 1.0 / npos : (sg[e] < 0 ? -1.0 / nneg : 0.0);
-    y[e] = 0.0;
-  }
-  double rp = 0.0, rd = 0.0;
-  int it = 0, st = 1;
-  while (it < max_iter) {
-    ++it;
-    double b[EPT], kb[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) b[e] = sg[e] != 0 ? rho * (z[e] - y[e]) : 0.0;
-    smv_kapply<EPT>(d, b, kb, t1, t2, pp, pn, m, sg, sc2, rc);
-    const double r1 = t1 - 1.0, r2 = t2 + 1.0;
-    const double nup = (r1 * a22 - r2 * a12) * rdet, nun = (a11 * r2 - a12 * r1) * rdet;
-    double sp = 0.0, sn = 0.0, ep = 0.0, ed = 0.0;
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      if (sg[e] != 0) {
-        const double x = __builtin_fma(-nun, pn[e], __builtin_fma(-nup, pp[e], kb[e]));
-        const double xv = x + y[e];
-        const double lo = sg[e] > 0 ? 0.0 : -u, hi = sg[e] > 0 ? u : 0.0;
-        const double zn = xv < lo ? lo : (xv > hi ? hi : xv);
-        ep = fmax(ep, fabs(x - zn));
-        ed = fmax(ed, rho * fabs(zn - z[e]));
-        y[e] = xv - zn;
-        z[e] = zn;
-        sp += sg[e] > 0 ? zn : 0.0;
-        sn += sg[e] < 0 ? zn : 0.0;
-      }
-    }
-    smv_put<true>(red, buf, sp, sn, ep, ed);
-    __syncthreads();
-    smv_get<true>(red, buf, sp, sn, rp, rd);
-    buf ^= 1;
-    // a leg-sum error moves the objective at first order (by the leg's multiplier), the split
-    // error |x - z| only through Sigma: the legs are held to eps / 10
-    const double eb = fmax(fabs(sp - 1.0), fabs(sn + 1.0));
-    const double gs = fmax(fabs(nup), fabs(nun));
-    const bool done = rp <= eps && eb <= 0.1 * eps && rd <= eps * gs;
-    rp = fmax(rp, eb);
-    rd = gs > 0.0 ? rd / gs : rd;
-    if (done) {
-      st = 0;
-      break;
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < EPT; ++e) {
-    const int a = tid + e * NT;
-    if (a < A) wj[a] = pr[e] ? z[e] : qnan();
-  }
-  if (tid == 0) {
-    counts[2 * j] = npos;
-    counts[2 * j + 1] = nneg;
-    inf[0] = (double)st;
-    inf[1] = (double)it;
-    inf[2] = rp;
-    inf[3] = rd;
-    inf[4] = delta;
-    inf[5] = rho;
-  }
+  // ---- p+-, the leg multipliers' system, ADMM from x0
+  double pp[EPT], pn[EPT], z[EPT], rp, rd;
+  int it;
+  const SmvApply<EPT> apply = {d, m, sg, sc2, 1.0 / (2.0 * delta + rho)};
+  const SmvLegs lg = smv_leg_system<EPT>(apply, d.red, d.buf, sg, pp, pn);
+  smv_admm<EPT>(apply, d.red, d.buf, sg, pp, pn, lg, npos, nneg, rho, u, max_iter, eps, z, st, it, rp, rd);
+  smv_write_row<EPT>(wj, A, pr, z);
+  smv_write_info(counts + 2 * j, info + 6 * j, npos, nneg, st, it, rp, rd, delta, rho);
 }
 
 }  // namespace fmx
@@ -231,35 +116,16 @@ extern "C" fmx_status fmx_sim_mvo_books(const double* R0, int64_t Dr, int64_t A,
   FMX_ARG(max_iter >= 1 && eps > 0.0, "sim_mvo: max_iter >= 1 and eps > 0");
   if (J == 0) return FMX_OK;
   hipStream_t s = as_stream(stream);
-  // the row lists are read back and checked: an index outside the panel is an argument error
-  {
-    std::vector<int32_t> ht((size_t)J), hr((size_t)(J * Lmax));
-    FMX_HIP(hipMemcpyAsync(ht.data(), win_T, sizeof(int32_t) * ht.size(), hipMemcpyDeviceToHost, s));
-    FMX_HIP(hipMemcpyAsync(hr.data(), win_rows, sizeof(int32_t) * hr.size(), hipMemcpyDeviceToHost, s));
-    FMX_HIP(hipStreamSynchronize(s));
-    for (int64_t j = 0; j < J; ++j) {
-      FMX_ARG(ht[j] >= 0 && ht[j] <= Lmax, "sim_mvo: win_T outside [0, Lmax]");
-      for (int32_t k = 0; k < ht[j]; ++k)
-        FMX_ARG(hr[j * Lmax + k] >= 0 && hr[j * Lmax + k] < Dr, "sim_mvo: window row index outside the returns panel");
-    }
-  }
+  if (fmx_status r = smv_check_windows(win_T, win_rows, J, Lmax, Dr, s, "sim_mvo")) return r;
   const bool m_in_lds = smv_lds_bytes(A, Lmax, true) <= SMV_LDS_MAX;
   double* mwork = nullptr;
   if (!m_in_lds) {
     FMX_ARG(work && work_bytes >= fmx_sim_mvo_books_work_bytes(A, Lmax, J), "sim_mvo: workspace too small");
     mwork = (double*)work;
   }
-  const size_t lds = smv_lds_bytes(A, Lmax, m_in_lds);
-  const int nt = A <= 256 ? 256 : (A <= 512 ? 512 : 1024);
-  const int ept = (int)ceil_div(A, nt);
-  const void* fn = ept <= 1 ? (const void*)k_sim_mvo<1> : ept <= 2 ? (const void*)k_sim_mvo<2>
-                 : ept <= 4 ? (const void*)k_sim_mvo<4> : ept <= 8 ? (const void*)k_sim_mvo<8>
-                            : (const void*)k_sim_mvo<16>;
-  if (lds > 64 * 1024) FMX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int Ai = (int)A, Li = (int)Lmax, mi = max_iter;
   void* args[] = {(void*)&R0, (void*)&Ai, (void*)&win_rows, (void*)&Li, (void*)&win_T, (void*)&X, (void*)&present,
                   (void*)&shrinkage, (void*)&max_weight, (void*)&mi, (void*)&eps, (void*)&W, (void*)&counts,
                   (void*)&info, (void*)&mwork};
-  FMX_HIP(hipLaunchKernel(fn, dim3((unsigned)J), dim3(nt), args, lds, s));
-  return FMX_OK;
+  return smv_launch(SMV_KERNEL(k_sim_mvo, A), J, smv_threads(A), args, smv_lds_bytes(A, Lmax, m_in_lds), s);
 }

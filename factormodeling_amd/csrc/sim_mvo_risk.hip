@@ -39,25 +39,6 @@ constexpr int RMV_KK = RMV_MAX_K * RMV_MAX_K;
 
 namespace {
 
-// smv_rowdot with the exposure row's non-finite cells read as 0
-__device__ __forceinline__ double rmv_rowdot(const double* vec, const double* __restrict__ r, int A) {
-  const int lane = threadIdx.x & 63;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  int a = lane;
-  for (; a + 192 < A; a += 256) {
-    const double r0 = r[a], r1 = r[a + 64], r2 = r[a + 128], r3 = r[a + 192];
-    a0 = __builtin_fma(vec[a], smv_finite(r0) ? r0 : 0.0, a0);
-    a1 = __builtin_fma(vec[a + 64], smv_finite(r1) ? r1 : 0.0, a1);
-    a2 = __builtin_fma(vec[a + 128], smv_finite(r2) ? r2 : 0.0, a2);
-    a3 = __builtin_fma(vec[a + 192], smv_finite(r3) ? r3 : 0.0, a3);
-  }
-  for (; a < A; a += 64) {
-    const double r0 = r[a];
-    a0 = __builtin_fma(vec[a], smv_finite(r0) ? r0 : 0.0, a0);
-  }
-  return smv_wsum((a0 + a1) + (a2 + a3));
-}
-
 // The workgroup's view of one date of the model.
 struct RmvDay {
   const double* Bd;   // B + model_row * A: row k at Bd + k * stride
@@ -102,7 +83,7 @@ __device__ __forceinline__ void rmv_gram(RmvDay& d, const double (&wgt)[EPT]) {
     }
     __syncthreads();
     for (int l = wv; l <= k; l += nw) {
-      const double v = rmv_rowdot(d.vec, d.Bd + l * d.stride, A);
+      const double v = smv_rowdot<true>(d.vec, d.Bd + l * d.stride, A);
       if (lane == 0) {
         d.G[k * K + l] = v;
         d.G[l * K + k] = v;
@@ -136,7 +117,7 @@ __device__ __forceinline__ void rmv_kapply(RmvDay& d, SmvDay& s, const double (&
   }
   smv_sum3(s.red, s.buf, t1, t2, z0);   // barrier inside: vec is complete
   for (int k = wv; k < K; k += nw) {
-    const double dd = rmv_rowdot(d.vec, d.Bd + k * d.stride, A);
+    const double dd = smv_rowdot<true>(d.vec, d.Bd + k * d.stride, A);
     if (lane == 0) d.gv[k] = dd;
   }
   __syncthreads();
@@ -165,6 +146,18 @@ __device__ __forceinline__ void rmv_kapply(RmvDay& d, SmvDay& s, const double (&
   for (int e = 0; e < EPT; ++e) out[e] = ie[e] != 0.0 ? (v[e] - acc[e]) * ie[e] : 0.0;
 }
 
+// rmv_kapply as the callable smv_leg_system and smv_admm take
+template <int EPT>
+struct RmvApply {
+  RmvDay& d;
+  SmvDay& s;
+  const double (&ie)[EPT];
+  __device__ __forceinline__ void operator()(const double (&v)[EPT], double (&out)[EPT], double& t1, double& t2,
+                                             const double (&pp)[EPT], const double (&pn)[EPT]) const {
+    rmv_kapply<EPT>(d, s, v, out, t1, t2, pp, pn, ie);
+  }
+};
+
 }  // namespace
 
 template <int EPT>
@@ -175,35 +168,30 @@ __global__ __launch_bounds__(1024) void k_risk_mvo(const double* __restrict__ B,
                                                    double eps, double* __restrict__ W, double* __restrict__ counts,
                                                    double* __restrict__ info) {
   extern __shared__ double sm[];
-  double* vec = sm;                          // [A]
-  double* gv = vec + A;                      // [SMV_MAX_T]
-  double* hv = gv + SMV_MAX_T;               // [SMV_MAX_T]
-  double* red = hv + SMV_MAX_T;              // [2 * SMV_RED]
-  double* G = sm + A + SMV_SMALL;            // [RMV_KK] x 3
+  const SmvLds l = smv_carve(sm, A);
+  double* gv = l.gv;
+  double* red = l.red;
+  double* G = l.tail;                        // [RMV_KK] x 3
   const int64_t j = blockIdx.x;
   const int tid = threadIdx.x, NT = blockDim.x;
   const int mr = model_row[j];
-  const double* xj = X + j * A;
-  const uint8_t* pj = present ? present + j * A : nullptr;
   double* wj = W + j * A;
-  double* inf = info + j * 6;
-  SmvDay s = {nullptr, A, K, nullptr, vec, gv, hv, red, G, 0};
+  SmvDay s = {nullptr, A, K, nullptr, l.vec, gv, l.hv, red, G, 0};
   int& buf = s.buf;
 
   // ---- the day's legs
   int sg[EPT];
   bool pr[EPT];
-  double cp, cn, cr;
-  smv_signs<EPT>(xj, pj, A, sg, pr, cp, cn, cr);
-  smv_sum3(red, buf, cp, cn, cr);
-  const double npos = cp, nneg = cn, npres = cr;
+  double npos, nneg, npres;
+  smv_signs<EPT>(X + j * A, present ? present + j * A : nullptr, A, sg, pr, npos, nneg, npres);
+  smv_sum3(red, buf, npos, nneg, npres);
 
   const bool flat = npos == 0.0 || nneg == 0.0 || npres < 2.0;
   const bool feasible = u * npos >= 1.0 - 1e-12 && u * nneg >= 1.0 - 1e-12;
   int st = flat ? 3 : (mr < 0 ? 4 : (feasible ? 0 : 2));
   double delta = 0.0, rho = 0.0, smax = -1.0, nsmin = -1.7e308;
   double ie[EPT];                           // 1 / E on the active cells, 0 elsewhere
-  RmvDay d = {B + (int64_t)(mr < 0 ? 0 : mr) * A, Dm * (int64_t)A, A, K, vec, gv, hv, G, G + RMV_KK, G + 2 * RMV_KK};
+  RmvDay d = {B + (int64_t)(mr < 0 ? 0 : mr) * A, Dm * (int64_t)A, A, K, l.vec, gv, l.hv, G, G + RMV_KK, G + 2 * RMV_KK};
 
   if (st == 0) {
     // ---- s2 on the active cells: finite, >= 0; its range
@@ -266,10 +254,7 @@ __global__ __launch_bounds__(1024) void k_risk_mvo(const double* __restrict__ B,
 #pragma unroll
       for (int e = 0; e < EPT; ++e) one[e] = sg[e] != 0 ? 1.0 : 0.0;
       rmv_gram<EPT>(d, one);
-      const double lmax = smv_lmax(s);
-      const double l_lo = 2.0 * delta, l_hi = 2.0 * smax + 2.0 * lmax;
-      const double ratio = l_lo > SMV_RATIO_FLOOR * l_hi ? l_lo / l_hi : SMV_RATIO_FLOOR;
-      rho = l_hi * sqrt(ratio);
+      rho = smv_rho(2.0 * delta, 2.0 * smax + 2.0 * smv_lmax(s));
       __syncthreads();
     }
     if (!(rho > 0.0) || !smv_finite(rho)) st = 2;
@@ -281,21 +266,10 @@ __global__ __launch_bounds__(1024) void k_risk_mvo(const double* __restrict__ B,
     rmv_gram<EPT>(d, ie);
     if (smv_sweep(s, 1.0, 1.0, rho)) st = 2;
   }
-  if (st != 0) {
+  if (st != 0) {   // no solve today: a zero row, or x0 on status 2
     const bool x0 = st == 2;
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      const int a = tid + e * NT;
-      if (a < A) wj[a] = pr[e] ? (x0 ? (sg[e] > 0 ? 1.0 / npos : (sg[e] < 0 ? -1.0 / nneg : 0.0)) : 0.0) : qnan();
-    }
-    if (tid == 0) {
-      counts[2 * j] = x0 ? npos : 0.0;
-      counts[2 * j + 1] = x0 ? nneg : 0.0;
-      inf[0] = (double)st;
-      inf[1] = inf[2] = inf[3] = 0.0;
-      inf[4] = delta;
-      inf[5] = rho;
-    }
+    smv_write_row<EPT>(wj, A, sg, pr, x0 ? 1.0 / npos : 0.0, x0 ? -1.0 / nneg : 0.0);
+    smv_write_info(counts + 2 * j, info + 6 * j, x0 ? npos : 0.0, x0 ? nneg : 0.0, st, 0, 0.0, 0.0, delta, rho);
     return;
   }
   for (int idx = tid; idx < K * K; idx += NT) G[idx] = -G[idx];
@@ -303,95 +277,14 @@ __global__ __launch_bounds__(1024) void k_risk_mvo(const double* __restrict__ B,
   rmv_mm<false, true>(d.Xb, d.G, d.L, K);
   rmv_mm<false, false>(d.G, d.L, d.Xb, K);
 
-  // ---- p+ = K^-1 e+, p- = K^-1 e-, and the 2 x 2 system of the leg multipliers
-  double pp[EPT], pn[EPT];
-  double t1, t2, a11 = 0.0, a12 = 0.0, a22 = 0.0;
-  {
-    double ev[EPT], o1[EPT], o2[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      pp[e] = pn[e] = 0.0;
-      ev[e] = sg[e] > 0 ? 1.0 : 0.0;
-    }
-    rmv_kapply<EPT>(d, s, ev, o1, t1, t2, pp, pn, ie);
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) ev[e] = sg[e] < 0 ? 1.0 : 0.0;
-    rmv_kapply<EPT>(d, s, ev, o2, t1, t2, pp, pn, ie);
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      pp[e] = o1[e];
-      pn[e] = o2[e];
-      a11 += sg[e] > 0 ? pp[e] : 0.0;
-      a12 += sg[e] > 0 ? pn[e] : 0.0;
-      a22 += sg[e] < 0 ? pn[e] : 0.0;
-    }
-    smv_sum3(red, buf, a11, a12, a22);
-  }
-  const double rdet = 1.0 / (a11 * a22 - a12 * a12);
-
-  // ---- ADMM from x0
-  double z[EPT], y[EPT];
-#pragma unroll
-  for (int e = 0; e < EPT; ++e) {
-    z[e] = sg[e] > 0 ? 1.0 / npos : (sg[e] < 0 ? -1.0 / nneg : 0.0);
-    y[e] = 0.0;
-  }
-  double rp = 0.0, rd = 0.0;
-  int it = 0;
-  st = 1;
-  while (it < max_iter) {
-    ++it;
-    double b[EPT], kb[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) b[e] = sg[e] != 0 ? rho * (z[e] - y[e]) : 0.0;
-    rmv_kapply<EPT>(d, s, b, kb, t1, t2, pp, pn, ie);
-    const double r1 = t1 - 1.0, r2 = t2 + 1.0;
-    const double nup = (r1 * a22 - r2 * a12) * rdet, nun = (a11 * r2 - a12 * r1) * rdet;
-    double sp = 0.0, sn = 0.0, ep = 0.0, ed = 0.0;
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      if (sg[e] != 0) {
-        const double x = __builtin_fma(-nun, pn[e], __builtin_fma(-nup, pp[e], kb[e]));
-        const double xv = x + y[e];
-        const double lo = sg[e] > 0 ? 0.0 : -u, hi = sg[e] > 0 ? u : 0.0;
-        const double zn = xv < lo ? lo : (xv > hi ? hi : xv);
-        ep = fmax(ep, fabs(x - zn));
-        ed = fmax(ed, rho * fabs(zn - z[e]));
-        y[e] = xv - zn;
-        z[e] = zn;
-        sp += sg[e] > 0 ? zn : 0.0;
-        sn += sg[e] < 0 ? zn : 0.0;
-      }
-    }
-    smv_put<true>(red, buf, sp, sn, ep, ed);
-    __syncthreads();
-    smv_get<true>(red, buf, sp, sn, rp, rd);
-    buf ^= 1;
-    const double eb = fmax(fabs(sp - 1.0), fabs(sn + 1.0));
-    const double gs = fmax(fabs(nup), fabs(nun));
-    const bool done = rp <= eps && eb <= 0.1 * eps && rd <= eps * gs;
-    rp = fmax(rp, eb);
-    rd = gs > 0.0 ? rd / gs : rd;
-    if (done) {
-      st = 0;
-      break;
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < EPT; ++e) {
-    const int a = tid + e * NT;
-    if (a < A) wj[a] = pr[e] ? z[e] : qnan();
-  }
-  if (tid == 0) {
-    counts[2 * j] = npos;
-    counts[2 * j + 1] = nneg;
-    inf[0] = (double)st;
-    inf[1] = (double)it;
-    inf[2] = rp;
-    inf[3] = rd;
-    inf[4] = delta;
-    inf[5] = rho;
-  }
+  // ---- p+-, the leg multipliers' system, ADMM from x0
+  double pp[EPT], pn[EPT], z[EPT], rp, rd;
+  int it;
+  const RmvApply<EPT> apply = {d, s, ie};
+  const SmvLegs lg = smv_leg_system<EPT>(apply, red, buf, sg, pp, pn);
+  smv_admm<EPT>(apply, red, buf, sg, pp, pn, lg, npos, nneg, rho, u, max_iter, eps, z, st, it, rp, rd);
+  smv_write_row<EPT>(wj, A, pr, z);
+  smv_write_info(counts + 2 * j, info + 6 * j, npos, nneg, st, it, rp, rd, delta, rho);
 }
 
 constexpr size_t rmv_lds_bytes(int64_t A) { return sizeof(double) * (size_t)(A + SMV_SMALL + 3 * RMV_KK); }
@@ -429,16 +322,8 @@ extern "C" fmx_status fmx_risk_mvo_books(const double* B, const double* Fc, cons
     FMX_HIP(hipStreamSynchronize(s));
     for (int64_t j = 0; j < J; ++j) FMX_ARG(hm[j] >= -1 && hm[j] < Dm, "risk_mvo: model_row outside [-1, Dm)");
   }
-  const size_t lds = rmv_lds_bytes(A);
-  const int nt = A <= 256 ? 256 : (A <= 512 ? 512 : 1024);
-  const int ept = (int)ceil_div(A, nt);
-  const void* fn = ept <= 1 ? (const void*)k_risk_mvo<1> : ept <= 2 ? (const void*)k_risk_mvo<2>
-                 : ept <= 4 ? (const void*)k_risk_mvo<4> : ept <= 8 ? (const void*)k_risk_mvo<8>
-                            : (const void*)k_risk_mvo<16>;
-  if (lds > 64 * 1024) FMX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int Ki = (int)K, Ai = (int)A, mi = max_iter;
   void* args[] = {(void*)&B, (void*)&Fc, (void*)&S2, (void*)&Ki, (void*)&Dm, (void*)&Ai, (void*)&model_row, (void*)&X,
                   (void*)&present, (void*)&max_weight, (void*)&mi, (void*)&eps, (void*)&W, (void*)&counts, (void*)&info};
-  FMX_HIP(hipLaunchKernel(fn, dim3((unsigned)J), dim3(nt), args, lds, s));
-  return FMX_OK;
+  return smv_launch(SMV_KERNEL(k_risk_mvo, A), J, smv_threads(A), args, rmv_lds_bytes(A), s);
 }

@@ -47,7 +47,6 @@
 // boxes hold the same books.
 // Caps as sim_mvo.hip: A <= 16,384, 1 <= Lmax <= 64.  Plain fp64, no cooperative launch.
 #include <cmath>
-#include <vector>
 
 #include "sim_mvo_common.hpp"
 
@@ -104,24 +103,18 @@ __global__ __launch_bounds__(1024) void k_smt_setup(const double* __restrict__ R
                                                     double* __restrict__ work, int64_t stride, int64_t wchain,
                                                     int skip_absent) {
   extern __shared__ double sm[];
-  double* vec = sm;                          // [A]
-  double* gv = vec + A;                      // [SMV_MAX_T]
-  double* hv = gv + SMV_MAX_T;               // [SMV_MAX_T]
-  double* red = hv + SMV_MAX_T;              // [2 * SMV_RED]
-  int* rows = (int*)(red + 2 * SMV_RED);     // [SMV_MAX_T]
+  const SmvLds l = smv_carve(sm, A);
   const int64_t bj = blockIdx.x;
   const int64_t wj = (bj / J) * wchain + bj % J;   // the date's row of the window tables (wchain 0: shared)
-  const int tid = threadIdx.x;
   const int T = win_T[wj];
   double* slot = work + bj * stride;
-  SmvDay d = {R0, A, T, rows, vec, gv, hv, red, slot + SMT_HDR, 0};
+  SmvDay d = {R0, A, T, l.rows, l.vec, l.gv, l.hv, l.red, slot + SMT_HDR, 0};
 
   int sg[EPT];
   bool pr[EPT];
-  double cp, cn, cr;
-  smv_signs<EPT>(X + bj * A, present ? present + bj * A : nullptr, A, sg, pr, cp, cn, cr);
-  smv_sum3(red, d.buf, cp, cn, cr);
-  const double npos = cp, nneg = cn, npres = cr;
+  double npos, nneg, npres;
+  smv_signs<EPT>(X + bj * A, present ? present + bj * A : nullptr, A, sg, pr, npos, nneg, npres);
+  smv_sum3(d.red, d.buf, npos, nneg, npres);
   const bool flat = npos == 0.0 || nneg == 0.0 || npres < 2.0;
   const bool feasible = u * npos >= 1.0 - 1e-12 && u * nneg >= 1.0 - 1e-12;
   double status = -1.0, delta = 0.0, sc2 = 0.0, rho = 0.0;
@@ -130,25 +123,10 @@ __global__ __launch_bounds__(1024) void k_smt_setup(const double* __restrict__ R
   } else if (flat || T <= 1 || !feasible) {
     status = flat ? 3.0 : (T == 0 ? 4.0 : 2.0);
   } else {
-    if (tid < T) rows[tid] = win_rows[wj * Lmax + tid];
-    __syncthreads();
     double m[EPT];
-    smv_col_means<EPT>(d, m);
-    double dsum = smv_diag_sum<EPT>(d, m, pr);
-    dsum = smv_sum(red, d.buf, dsum);
-    const double avg_var = dsum / ((double)(T - 1) * npres) + 1e-6;
-    const double q = shrink > 0.0 ? 1.0 - shrink : 1.0;
-    delta = q * 1e-6 + (shrink > 0.0 ? shrink * avg_var : 0.0);
-    sc2 = q / (double)(T - 1);
-    smv_gram<EPT>(d, m, sg);
-    rho = smv_rho(delta, sc2, smv_lmax(d));
-    if (smv_sweep(d, 2.0 * delta + rho, sc2, rho)) {
-      status = 2.0;   // a non-finite return in the window: x0 (:451-459)
-    } else {
-      for (int idx = tid; idx < T * T; idx += blockDim.x) d.M[idx] = -d.M[idx];
-    }
+    if (smv_window_setup<EPT>(d, win_rows + wj * Lmax, sg, pr, npres, shrink, m, delta, sc2, rho)) status = 2.0;
   }
-  if (tid == 0) {
+  if (threadIdx.x == 0) {
     slot[0] = status;
     slot[1] = npos;
     slot[2] = nneg;
@@ -168,12 +146,9 @@ __global__ __launch_bounds__(1024) void k_smt_chain(const double* __restrict__ R
                                                     const double* work, int64_t stride, int m_in_lds,
                                                     int64_t wchain) {
   extern __shared__ double sm[];
-  double* vec = sm;                          // [A]
-  double* gv = vec + A;                      // [SMV_MAX_T]
-  double* hv = gv + SMV_MAX_T;               // [SMV_MAX_T]
-  double* red = hv + SMV_MAX_T;              // [2 * SMV_RED]
-  int* rows = (int*)(red + 2 * SMV_RED);     // [SMV_MAX_T]
-  double* red5 = sm + A + SMV_SMALL;         // [2 * SMT_RED5]
+  const SmvLds l = smv_carve(sm, A);
+  double* red = l.red;
+  double* red5 = l.tail;                     // [2 * SMT_RED5]
   double* Mlds = red5 + 2 * SMT_RED5;        // [Lmax * Lmax] when m_in_lds
   const int64_t b = blockIdx.x;
   const int tid = threadIdx.x, NT = blockDim.x;
@@ -206,11 +181,7 @@ __global__ __launch_bounds__(1024) void k_smt_chain(const double* __restrict__ R
           if (oj) oj[a] = qnan();
         }
       }
-      if (tid == 0) {
-        counts[2 * bj] = counts[2 * bj + 1] = qnan();
-        inf[0] = 5.0;
-        inf[1] = inf[2] = inf[3] = inf[4] = inf[5] = 0.0;
-      }
+      smv_write_info(counts + 2 * bj, inf, qnan(), qnan(), 5, 0, 0.0, 0.0, 0.0, 0.0);
       continue;
     }
 
@@ -222,7 +193,9 @@ __global__ __launch_bounds__(1024) void k_smt_chain(const double* __restrict__ R
     }
 
     if (st0 >= 0) {   // no solve today: flat (3), the caller's equal-weight row (4) or x0 (2)
-      const double wl = st0 == 2 ? 1.0 / npos : 0.0, ws = st0 == 2 ? -1.0 / nneg : 0.0;
+      const bool x0 = st0 == 2;
+      const double wl = x0 ? 1.0 / npos : 0.0, ws = x0 ? -1.0 / nneg : 0.0;
+      if (st0 != 4) smv_write_row<EPT>(wj, A, sg, pr, wl, ws);
 #pragma unroll
       for (int e = 0; e < EPT; ++e) {
         const int a = tid + e * NT;
@@ -231,37 +204,26 @@ __global__ __launch_bounds__(1024) void k_smt_chain(const double* __restrict__ R
           if (st0 == 4) {
             v = wj[a];
             if (!smv_finite(v)) v = 0.0;
-          } else {
-            wj[a] = pr[e] ? v : qnan();
           }
           if (oj) oj[a] = pr[e] ? v : qnan();
           book[e] = pr[e] ? v : 0.0;
         }
       }
-      if (tid == 0) {
-        counts[2 * bj] = st0 == 2 ? npos : 0.0;
-        counts[2 * bj + 1] = st0 == 2 ? nneg : 0.0;
-        inf[0] = (double)st0;
-        inf[1] = inf[2] = inf[3] = 0.0;
-        inf[4] = delta;
-        inf[5] = rho;
-      }
+      smv_write_info(counts + 2 * bj, inf, x0 ? npos : 0.0, x0 ? nneg : 0.0, st0, 0, 0.0, 0.0, delta, rho);
       continue;
     }
 
     // ---- the window, M^-1 from the set-up, p+-, the 2 x 2 system
-    if (tid < T) rows[tid] = win_rows[wr * Lmax + tid];
+    if (tid < T) l.rows[tid] = win_rows[wr * Lmax + tid];
     const double* Ms = slot + SMT_HDR;
     if (m_in_lds)
       for (int idx = tid; idx < T * T; idx += NT) Mlds[idx] = Ms[idx];
     __syncthreads();
-    SmvDay d = {R0, A, T, rows, vec, gv, hv, red, m_in_lds ? Mlds : const_cast<double*>(Ms), buf};
+    SmvDay d = {R0, A, T, l.rows, l.vec, l.gv, l.hv, red, m_in_lds ? Mlds : const_cast<double*>(Ms), buf};
     double m[EPT], pp[EPT], pn[EPT];
     smv_col_means<EPT>(d, m);
-    const double c = 2.0 * delta + rho, rc = 1.0 / c;
-    double t1, t2, a11, a12, a22;
-    smv_leg_system<EPT>(d, pp, pn, m, sg, sc2, rc, a11, a12, a22);
-    const double rdet = 1.0 / (a11 * a22 - a12 * a12);
+    const SmvApply<EPT> apply = {d, m, sg, sc2, 1.0 / (2.0 * delta + rho)};
+    const SmvLegs lg = smv_leg_system<EPT>(apply, red, d.buf, sg, pp, pn);
 
     // ---- the start: z = x0 and the dual of a leg that has to move one way, y0 = s tau / rho
     // (s = +-1 per leg, 0 for a leg already on target).  y0 is never added to anything: in the
@@ -297,7 +259,7 @@ __global__ __launch_bounds__(1024) void k_smt_chain(const double* __restrict__ R
     int it = 0, st = 1;
     while (it < max_iter) {
       ++it;
-      double bv[EPT], kb[EPT];
+      double bv[EPT], kb[EPT], t1, t2, nup, nun;
       if (rw != 0.0) {
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
@@ -308,9 +270,8 @@ __global__ __launch_bounds__(1024) void k_smt_chain(const double* __restrict__ R
 #pragma unroll
         for (int e = 0; e < EPT; ++e) bv[e] = sg[e] != 0 ? rho * (z[e] - y[e]) : 0.0;
       }
-      smv_kapply<EPT>(d, bv, kb, t1, t2, pp, pn, m, sg, sc2, rc);
-      const double r1 = t1 - 1.0, r2 = t2 + 1.0;
-      const double nup = (r1 * a22 - r2 * a12) * rdet, nun = (a11 * r2 - a12 * r1) * rdet;
+      apply(bv, kb, t1, t2, pp, pn);
+      lg.nu(t1, t2, nup, nun);
       double sp = 0.0, sn = 0.0, ep = 0.0, ed = 0.0, eq = 0.0;
 #pragma unroll
       for (int e = 0; e < EPT; ++e) {
@@ -336,11 +297,7 @@ __global__ __launch_bounds__(1024) void k_smt_chain(const double* __restrict__ R
       __syncthreads();
       smt_get5(red5, buf5, sp, sn, rp, rd, gs);
       buf5 ^= 1;
-      const double eb = fmax(fabs(sp - 1.0), fabs(sn + 1.0));
-      const bool done = rp <= eps && eb <= 0.1 * eps && rd <= eps * gs;
-      rp = fmax(rp, eb);
-      rd = gs > 0.0 ? rd / gs : rd;
-      if (done) {
+      if (smv_stop(sp, sn, gs, eps, rp, rd)) {
         st = 0;
         break;
       }
@@ -376,16 +333,7 @@ __global__ __launch_bounds__(1024) void k_smt_chain(const double* __restrict__ R
         book[e] = pr[e] ? v : 0.0;
       }
     }
-    if (tid == 0) {
-      counts[2 * bj] = npos;
-      counts[2 * bj + 1] = nneg;
-      inf[0] = (double)st;
-      inf[1] = (double)it;
-      inf[2] = rp;
-      inf[3] = rd;
-      inf[4] = delta;
-      inf[5] = rho;
-    }
+    smv_write_info(counts + 2 * bj, inf, npos, nneg, st, it, rp, rd, delta, rho);
     buf = d.buf;
   }
 }
@@ -428,50 +376,27 @@ static fmx_status smt_run(const double* R0, int64_t Dr, int64_t A, const int32_t
   FMX_ARG(win_stride == 0 || win_stride == J, "sim_mvo_turnover: the window tables' chain stride must be 0 or J");
   if (J == 0 || B == 0) return FMX_OK;
   hipStream_t s = as_stream(stream);
-  // the row lists are read back and checked: an index outside the panel is an argument error
   const int64_t NR = win_stride == 0 ? J : B * J;   // rows of the window tables
-  {
-    std::vector<int32_t> ht((size_t)NR), hr((size_t)(NR * Lmax));
-    FMX_HIP(hipMemcpyAsync(ht.data(), win_T, sizeof(int32_t) * ht.size(), hipMemcpyDeviceToHost, s));
-    FMX_HIP(hipMemcpyAsync(hr.data(), win_rows, sizeof(int32_t) * hr.size(), hipMemcpyDeviceToHost, s));
-    FMX_HIP(hipStreamSynchronize(s));
-    for (int64_t j = 0; j < NR; ++j) {
-      FMX_ARG(ht[j] >= 0 && ht[j] <= Lmax, "sim_mvo_turnover: win_T outside [0, Lmax]");
-      for (int32_t k = 0; k < ht[j]; ++k)
-        FMX_ARG(hr[j * Lmax + k] >= 0 && hr[j * Lmax + k] < Dr,
-                "sim_mvo_turnover: window row index outside the returns panel");
-    }
-  }
+  if (fmx_status r = smv_check_windows(win_T, win_rows, NR, Lmax, Dr, s, "sim_mvo_turnover")) return r;
   FMX_ARG(work && work_bytes >= fmx_sim_mvo_turnover_books_work_bytes(A, Lmax, J, B),
           "sim_mvo_turnover: workspace too small");
   double* wk = (double*)work;
   const int64_t stride = SMT_HDR + Lmax * Lmax;
   const int m_in_lds = smt_lds_bytes(A, Lmax, true) <= SMV_LDS_MAX ? 1 : 0;
   const size_t lds_setup = smv_lds_bytes(A, Lmax, false), lds_chain = smt_lds_bytes(A, Lmax, m_in_lds != 0);
-  const int nt = A <= 256 ? 256 : (A <= 512 ? 512 : 1024);
-  const int ept = (int)ceil_div(A, nt);
-  const void* fs = ept <= 1 ? (const void*)k_smt_setup<1> : ept <= 2 ? (const void*)k_smt_setup<2>
-                 : ept <= 4 ? (const void*)k_smt_setup<4> : ept <= 8 ? (const void*)k_smt_setup<8>
-                            : (const void*)k_smt_setup<16>;
-  const void* fc = ept <= 1 ? (const void*)k_smt_chain<1> : ept <= 2 ? (const void*)k_smt_chain<2>
-                 : ept <= 4 ? (const void*)k_smt_chain<4> : ept <= 8 ? (const void*)k_smt_chain<8>
-                            : (const void*)k_smt_chain<16>;
-  if (lds_setup > 64 * 1024)
-    FMX_HIP(hipFuncSetAttribute(fs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_setup));
-  if (lds_chain > 64 * 1024)
-    FMX_HIP(hipFuncSetAttribute(fc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_chain));
   int Ai = (int)A, Li = (int)Lmax, Ji = (int)J, mi = max_iter, ml = m_in_lds;
   int64_t st = stride, wc = win_stride;
   int sk = skip_absent ? 1 : 0;
   void* a1[] = {(void*)&R0, (void*)&Ai, (void*)&win_rows, (void*)&Li, (void*)&win_T, (void*)&X, (void*)&present,
                 (void*)&Ji, (void*)&shrinkage, (void*)&max_weight, (void*)&wk, (void*)&st, (void*)&wc, (void*)&sk};
-  FMX_HIP(hipLaunchKernel(fs, dim3((unsigned)(B * J)), dim3(nt), a1, lds_setup, s));
+  // the chain kernel's LDS attribute is raised after the set-up launch: if that fails, the set-up
+  // has only written its workspace slots
+  if (fmx_status r = smv_launch(SMV_KERNEL(k_smt_setup, A), B * J, smv_threads(A), a1, lds_setup, s)) return r;
   void* a2[] = {(void*)&R0, (void*)&Ai, (void*)&win_rows, (void*)&Li, (void*)&win_T, (void*)&X, (void*)&present,
                 (void*)&Ji, (void*)&max_weight, (void*)&turnover_penalty, (void*)&return_weight, (void*)&mi,
                 (void*)&eps, (void*)&W, (void*)&Wopt, (void*)&counts, (void*)&info, (void*)&wk, (void*)&st, (void*)&ml,
                 (void*)&wc};
-  FMX_HIP(hipLaunchKernel(fc, dim3((unsigned)B), dim3(nt), a2, lds_chain, s));
-  return FMX_OK;
+  return smv_launch(SMV_KERNEL(k_smt_chain, A), B, smv_threads(A), a2, lds_chain, s);
 }
 
 extern "C" fmx_status fmx_sim_mvo_turnover_books(const double* R0, int64_t Dr, int64_t A, const int32_t* win_rows,

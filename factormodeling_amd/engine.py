@@ -1142,6 +1142,45 @@ SIM_MVO_MAX_A = 16384
 SIM_MVO_MAX_T = 64
 
 
+def _is_f64_device(t, dims, device=None):
+    """t is a float64 tensor with t.dim() in dims on ``device`` (None: any HIP device)."""
+    return (isinstance(t, torch.Tensor) and t.dtype == F64 and t.dim() in dims
+            and (t.device.type == "cuda" if device is None else t.device == device))
+
+
+def _mvo_assets(fn, first, A, XA):
+    if XA != A or not 1 <= A <= SIM_MVO_MAX_A:
+        raise _lib.FmxError(f"{fn}: {first} and X must share 1 <= A <= {SIM_MVO_MAX_A} asset columns")
+
+
+def _check_present_chains(present, B, J, A):
+    if present is not None:
+        if present.dtype != torch.uint8 or tuple(as3(present).shape) != (B, J, A) or not present.is_contiguous():
+            raise _lib.FmxError("present must be a contiguous uint8 [B][J][A] device tensor")
+
+
+def _mvo_windows(fn, win_rows, win_T, device, J, B=None):
+    """The window tables as contiguous int32 device tensors, win_rows [J][Lmax] / win_T [J] or,
+    when ``B`` is given, also [B][J][Lmax] / [B][J].  Returns (win_rows, win_T, Lmax, shared)."""
+    win_rows = torch.as_tensor(win_rows, dtype=torch.int32).to(device).contiguous()
+    win_T = torch.as_tensor(win_T, dtype=torch.int32).to(device).contiguous()
+    shared = B is None or win_T.dim() == 1
+    lead = (J,) if shared else (B, J)
+    if win_rows.dim() != len(lead) + 1 or tuple(win_rows.shape[:-1]) != lead or tuple(win_T.shape) != lead:
+        raise _lib.FmxError(f"{fn}: win_rows must be [J][Lmax] and win_T [J]" if B is None else
+                            f"{fn}: win_rows must be [B][J][Lmax] and win_T [B][J] "
+                            "(or [J][Lmax] and [J], shared by the chains)")
+    Lmax = int(win_rows.shape[-1])
+    if not 1 <= Lmax <= SIM_MVO_MAX_T:
+        raise _lib.FmxError(f"{fn}: 1 <= Lmax <= {SIM_MVO_MAX_T} window rows supported, got {Lmax}")
+    return win_rows, win_T, Lmax, shared
+
+
+def _mvo_outputs(lead, lasts, device):
+    """One uninitialised float64 tensor lead + (n,) per n in lasts: W (A), counts (2), info (6)."""
+    return [torch.empty(tuple(lead) + (n,), dtype=F64, device=device) for n in lasts]
+
+
 def sim_mvo_books(R0, win_rows, win_T, X, present=None, shrinkage=0.1, max_weight=0.03, max_iter=20000, eps=1e-9):
     """Simulation._daily_trade_list, method 'mvo' (portfolio_simulation.py:183-204, :315-461)
     for J dates in one launch (fmx_sim_mvo_books): R0 [Dr][A] the zero-filled returns panel,
@@ -1151,23 +1190,14 @@ def sim_mvo_books(R0, win_rows, win_T, X, present=None, shrinkage=0.1, max_weigh
     residual relative to the leg multipliers, delta, rho).  status 0 converged, 1 max_iter reached, 2 x0 fallback, 3 flat day,
     4 no returns history (the caller supplies the equal-weight book)."""
     for t, name in ((R0, "R0"), (X, "X")):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != F64 or t.dim() != 2:
+        if not _is_f64_device(t, (2,)):
             raise _lib.FmxError(f"sim_mvo_books: {name} must be a float64 2-D HIP device tensor")
     R0, X = R0.contiguous(), X.contiguous()
     (Dr, A), J = R0.shape, X.shape[0]
-    if X.shape[1] != A or not 1 <= A <= SIM_MVO_MAX_A:
-        raise _lib.FmxError(f"sim_mvo_books: R0 and X must share 1 <= A <= {SIM_MVO_MAX_A} asset columns")
+    _mvo_assets("sim_mvo_books", "R0", A, X.shape[1])
     _check_present(present, J, A)
-    win_rows = torch.as_tensor(win_rows, dtype=torch.int32).to(X.device).contiguous()
-    win_T = torch.as_tensor(win_T, dtype=torch.int32).to(X.device).contiguous()
-    if win_rows.dim() != 2 or win_rows.shape[0] != J or tuple(win_T.shape) != (J,):
-        raise _lib.FmxError("sim_mvo_books: win_rows must be [J][Lmax] and win_T [J]")
-    Lmax = int(win_rows.shape[1])
-    if not 1 <= Lmax <= SIM_MVO_MAX_T:
-        raise _lib.FmxError(f"sim_mvo_books: 1 <= Lmax <= {SIM_MVO_MAX_T} window rows supported, got {Lmax}")
-    W = torch.empty((J, A), dtype=F64, device=X.device)
-    counts = torch.empty((J, 2), dtype=F64, device=X.device)
-    info = torch.empty((J, 6), dtype=F64, device=X.device)
+    win_rows, win_T, Lmax, _ = _mvo_windows("sim_mvo_books", win_rows, win_T, X.device, J)
+    W, counts, info = _mvo_outputs((J,), (A, 2, 6), X.device)
     nb = int(_lib.load().fmx_sim_mvo_books_work_bytes(A, Lmax, J))
     work, wb = _workspace_bytes(X.device, nb)
     call("fmx_sim_mvo_books", ptr(R0), int(Dr), int(A), ptr(win_rows), ptr(win_T), Lmax, ptr(X), ptr(present), int(J),
@@ -1230,12 +1260,11 @@ def risk_mvo_books(B, Fc, S2, X, present=None, model_row=None, max_weight=0.03, 
     (W [J][A], counts [J][2], info [J][6]) as ``sim_mvo_books`` (info[:, 4] = the smallest
     specific variance of the active cells).  A model_row outside [-1, Dm) raises FmxError."""
     K, Dm, A = _check_risk_model("risk_mvo_books", B, Fc, S2)
-    if not isinstance(X, torch.Tensor) or X.device != B.device or X.dtype != F64 or X.dim() != 2:
+    if not _is_f64_device(X, (2,), B.device):
         raise _lib.FmxError("risk_mvo_books: X must be a float64 [J][A] tensor on B's device")
     X = X.contiguous()
     J = X.shape[0]
-    if X.shape[1] != A or not 1 <= A <= SIM_MVO_MAX_A:
-        raise _lib.FmxError(f"risk_mvo_books: B and X must share 1 <= A <= {SIM_MVO_MAX_A} asset columns")
+    _mvo_assets("risk_mvo_books", "B", A, X.shape[1])
     _check_present(present, J, A)
     if model_row is None:
         if J != Dm:
@@ -1244,12 +1273,32 @@ def risk_mvo_books(B, Fc, S2, X, present=None, model_row=None, max_weight=0.03, 
     model_row = torch.as_tensor(model_row, dtype=torch.int32).to(X.device).contiguous()
     if tuple(model_row.shape) != (J,):
         raise _lib.FmxError(f"risk_mvo_books: model_row must be [{J}]")
-    W = torch.empty((J, A), dtype=F64, device=X.device)
-    counts = torch.empty((J, 2), dtype=F64, device=X.device)
-    info = torch.empty((J, 6), dtype=F64, device=X.device)
+    W, counts, info = _mvo_outputs((J,), (A, 2, 6), X.device)
     call("fmx_risk_mvo_books", ptr(B), ptr(Fc), ptr(S2), int(K), int(Dm), int(A), ptr(model_row), ptr(X), ptr(present),
          int(J), float(max_weight), int(max_iter), float(eps), ptr(W), ptr(counts), ptr(info), stream_ptr())
     return W, counts, info
+
+
+def _mvo_turnover_inputs(fn, R0, win_rows, win_T, X, present, W, return_opt, chain_windows):
+    """What ``sim_mvo_turnover_books`` and ``sim_mvo_turnover_chains`` (``fn``, for the error
+    texts) check and allocate alike.  ``chain_windows``: the window tables may be per chain.
+    Returns (R0, win_rows, win_T, Lmax, shared, X, W, Wopt, counts, info)."""
+    for t, name, nd in ((R0, "R0", (2,)), (X, "X", (2, 3))):
+        if not _is_f64_device(t, nd):
+            raise _lib.FmxError(f"{fn}: {name} must be a float64 HIP device tensor "
+                                f"({' or '.join(str(n) for n in nd)}-D)")
+    R0, X = R0.contiguous(), as3(X).contiguous()
+    A, (B, J, _) = R0.shape[1], X.shape
+    _mvo_assets(fn, "R0", A, X.shape[2])
+    _check_present_chains(present, B, J, A)
+    win_rows, win_T, Lmax, shared = _mvo_windows(fn, win_rows, win_T, X.device, J, B if chain_windows else None)
+    if W is None:
+        W = torch.zeros((B, J, A), dtype=F64, device=X.device)
+    elif not _is_f64_device(W, (2, 3), X.device) or tuple(as3(W).shape) != (B, J, A) or not W.is_contiguous():
+        raise _lib.FmxError(f"{fn}: W must be a contiguous float64 [B][J][A] tensor on X's device")
+    Wopt = torch.empty((B, J, A), dtype=F64, device=X.device) if return_opt else None
+    counts, info = _mvo_outputs((B, J), (2, 6), X.device)
+    return R0, win_rows, win_T, Lmax, shared, X, as3(W), Wopt, counts, info
 
 
 def sim_mvo_turnover_books(R0, win_rows, win_T, X, present=None, W=None, shrinkage=0.1, max_weight=0.03,
@@ -1262,33 +1311,9 @@ def sim_mvo_turnover_books(R0, win_rows, win_T, X, present=None, W=None, shrinka
     the kernel reads those rows as the next date's previous weights and writes every other row.
     Returns (W, counts [B][J][2], info [B][J][6]) and, with ``return_opt``, Wopt [B][J][A]: the
     solver's iterate before the prune / renormalise step."""
-    for t, name, nd in ((R0, "R0", (2,)), (X, "X", (2, 3))):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != F64 or t.dim() not in nd:
-            raise _lib.FmxError(f"sim_mvo_turnover_books: {name} must be a float64 HIP device tensor "
-                                f"({' or '.join(str(n) for n in nd)}-D)")
-    R0, X = R0.contiguous(), as3(X).contiguous()
+    R0, win_rows, win_T, Lmax, _, X, W, Wopt, counts, info = _mvo_turnover_inputs(
+        "sim_mvo_turnover_books", R0, win_rows, win_T, X, present, W, return_opt, chain_windows=False)
     (Dr, A), (B, J, _) = R0.shape, X.shape
-    if X.shape[2] != A or not 1 <= A <= SIM_MVO_MAX_A:
-        raise _lib.FmxError(f"sim_mvo_turnover_books: R0 and X must share 1 <= A <= {SIM_MVO_MAX_A} asset columns")
-    if present is not None:
-        if present.dtype != torch.uint8 or tuple(as3(present).shape) != (B, J, A) or not present.is_contiguous():
-            raise _lib.FmxError("present must be a contiguous uint8 [B][J][A] device tensor")
-    win_rows = torch.as_tensor(win_rows, dtype=torch.int32).to(X.device).contiguous()
-    win_T = torch.as_tensor(win_T, dtype=torch.int32).to(X.device).contiguous()
-    if win_rows.dim() != 2 or win_rows.shape[0] != J or tuple(win_T.shape) != (J,):
-        raise _lib.FmxError("sim_mvo_turnover_books: win_rows must be [J][Lmax] and win_T [J]")
-    Lmax = int(win_rows.shape[1])
-    if not 1 <= Lmax <= SIM_MVO_MAX_T:
-        raise _lib.FmxError(f"sim_mvo_turnover_books: 1 <= Lmax <= {SIM_MVO_MAX_T} window rows supported, got {Lmax}")
-    if W is None:
-        W = torch.zeros((B, J, A), dtype=F64, device=X.device)
-    elif (not isinstance(W, torch.Tensor) or W.device != X.device or W.dtype != F64 or tuple(as3(W).shape) != (B, J, A)
-          or not W.is_contiguous()):
-        raise _lib.FmxError("sim_mvo_turnover_books: W must be a contiguous float64 [B][J][A] tensor on X's device")
-    W = as3(W)
-    Wopt = torch.empty((B, J, A), dtype=F64, device=X.device) if return_opt else None
-    counts = torch.empty((B, J, 2), dtype=F64, device=X.device)
-    info = torch.empty((B, J, 6), dtype=F64, device=X.device)
     nb = int(_lib.load().fmx_sim_mvo_turnover_books_work_bytes(A, Lmax, J, B))
     work, wb = _workspace_bytes(X.device, nb)
     call("fmx_sim_mvo_turnover_books", ptr(R0), int(Dr), int(A), ptr(win_rows), ptr(win_T), Lmax, ptr(X), ptr(present),
@@ -1306,39 +1331,9 @@ def sim_mvo_turnover_chains(R0, win_rows, win_T, X, present=None, W=None, shrink
     date) without a present cell is not a date of that chain: NaN row, NaN counts, info[0] = 5,
     and the chain's previous book stays the one of its last date with rows.  Returns
     (W [B][J][A], counts [B][J][2], info [B][J][6]) and Wopt with ``return_opt``."""
-    for t, name, nd in ((R0, "R0", (2,)), (X, "X", (2, 3))):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != F64 or t.dim() not in nd:
-            raise _lib.FmxError(f"sim_mvo_turnover_chains: {name} must be a float64 HIP device tensor "
-                                f"({' or '.join(str(n) for n in nd)}-D)")
-    R0, X = R0.contiguous(), as3(X).contiguous()
+    R0, win_rows, win_T, Lmax, shared, X, W, Wopt, counts, info = _mvo_turnover_inputs(
+        "sim_mvo_turnover_chains", R0, win_rows, win_T, X, present, W, return_opt, chain_windows=True)
     (Dr, A), (B, J, _) = R0.shape, X.shape
-    if X.shape[2] != A or not 1 <= A <= SIM_MVO_MAX_A:
-        raise _lib.FmxError(f"sim_mvo_turnover_chains: R0 and X must share 1 <= A <= {SIM_MVO_MAX_A} asset columns")
-    if present is not None:
-        if present.dtype != torch.uint8 or tuple(as3(present).shape) != (B, J, A) or not present.is_contiguous():
-            raise _lib.FmxError("present must be a contiguous uint8 [B][J][A] device tensor")
-    win_rows = torch.as_tensor(win_rows, dtype=torch.int32).to(X.device).contiguous()
-    win_T = torch.as_tensor(win_T, dtype=torch.int32).to(X.device).contiguous()
-    shared = win_T.dim() == 1
-    if shared:
-        ok = win_rows.dim() == 2 and win_rows.shape[0] == J and tuple(win_T.shape) == (J,)
-    else:
-        ok = win_rows.dim() == 3 and tuple(win_rows.shape[:2]) == (B, J) and tuple(win_T.shape) == (B, J)
-    if not ok:
-        raise _lib.FmxError("sim_mvo_turnover_chains: win_rows must be [B][J][Lmax] and win_T [B][J] "
-                            "(or [J][Lmax] and [J], shared by the chains)")
-    Lmax = int(win_rows.shape[-1])
-    if not 1 <= Lmax <= SIM_MVO_MAX_T:
-        raise _lib.FmxError(f"sim_mvo_turnover_chains: 1 <= Lmax <= {SIM_MVO_MAX_T} window rows supported, got {Lmax}")
-    if W is None:
-        W = torch.zeros((B, J, A), dtype=F64, device=X.device)
-    elif (not isinstance(W, torch.Tensor) or W.device != X.device or W.dtype != F64 or tuple(as3(W).shape) != (B, J, A)
-          or not W.is_contiguous()):
-        raise _lib.FmxError("sim_mvo_turnover_chains: W must be a contiguous float64 [B][J][A] tensor on X's device")
-    W = as3(W)
-    Wopt = torch.empty((B, J, A), dtype=F64, device=X.device) if return_opt else None
-    counts = torch.empty((B, J, 2), dtype=F64, device=X.device)
-    info = torch.empty((B, J, 6), dtype=F64, device=X.device)
     nb = int(_lib.load().fmx_sim_mvo_turnover_chains_work_bytes(A, Lmax, J, B))
     work, wb = _workspace_bytes(X.device, nb)
     call("fmx_sim_mvo_turnover_chains", ptr(R0), int(Dr), int(A), ptr(win_rows), ptr(win_T), Lmax, 0 if shared else int(J),
