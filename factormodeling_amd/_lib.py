@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FMX_LIB", os.path.join(_HERE, "libfmx.so"))
 
 c_i32, c_i64, c_dbl, c_vp, c_cp = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_char_p
+c_u32 = ctypes.c_uint32
 
 # name -> argtypes (restype is c_int32 = fmx_status unless listed in _RESTYPES)
 SIGNATURES = {
@@ -130,6 +131,9 @@ SIGNATURES = {
     "fmx_risk_mvo_books": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl, c_i32, c_dbl, c_vp,
                            c_vp, c_vp, c_vp],
     "fmx_risk_mvo_books_work_bytes": [c_i64, c_i64, c_i64],
+    "fmx_risk_mvo_neutral_books": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_u32, c_dbl, c_i32,
+                                   c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "fmx_risk_mvo_neutral_books_work_bytes": [c_i64, c_i64, c_i64],
 }
 _RESTYPES = {"fmx_last_error": c_cp, "fmx_build_variant": c_cp, "fmx_ic_ranked_work_len": c_i64, "fmx_rank_ic_work_len": c_i64, "fmx_gram_work_bytes": c_i64, "fmx_gram_direct_work_bytes": c_i64,
              "fmx_gram_direct_exact_work_bytes": c_i64, "fmx_ic_daily_sorted_work_bytes": c_i64,
@@ -140,6 +144,7 @@ _RESTYPES = {"fmx_last_error": c_cp, "fmx_build_variant": c_cp, "fmx_ic_ranked_w
              "fmx_mvo_windows_work_bytes": c_i64, "fmx_sim_mvo_books_work_bytes": c_i64,
              "fmx_sim_mvo_turnover_books_work_bytes": c_i64, "fmx_sim_mvo_turnover_chains_work_bytes": c_i64,
              "fmx_sim_mvo_window_rows_work_bytes": c_i64, "fmx_risk_mvo_books_work_bytes": c_i64,
+             "fmx_risk_mvo_neutral_books_work_bytes": c_i64,
              "fmx_debug_exact_fold": None}
 
 # constants mirrored from include/fmx.h

@@ -1252,13 +1252,17 @@ def risk_books(B, Fc, S2, W, present=None, valid=None, marginal=False):
     return out
 
 
-def risk_mvo_books(B, Fc, S2, X, present=None, model_row=None, max_weight=0.03, max_iter=20000, eps=1e-9):
+def risk_mvo_books(B, Fc, S2, X, present=None, model_row=None, max_weight=0.03, max_iter=20000, eps=1e-9,
+                   neutral=None, return_expo=False):
     """``sim_mvo_books``' QP against the factor model (fmx_risk_mvo_books): book j is
     the minimum-variance long/short book of signal X[j] under diag(S2[r]) + B[:, r]' Fc[r] B[:, r],
     r = model_row[j] (default: j, for a model with one date per book; -1: no model, status 4).
     B [K][Dm][A], Fc [Dm][K][K], S2 [Dm][A], X [J][A], present [J][A] uint8 or None.  Returns
     (W [J][A], counts [J][2], info [J][6]) as ``sim_mvo_books`` (info[:, 4] = the smallest
-    specific variance of the active cells).  A model_row outside [-1, Dm) raises FmxError."""
+    specific variance of the active cells).  A model_row outside [-1, Dm) raises FmxError.
+    ``neutral``: factor indices k the book is also neutral to, B[k, r] . w = 0 on the active cells
+    (fmx_risk_mvo_neutral_books); a date on which that is infeasible ends with status
+    1.  ``return_expo`` appends expo [J][K] = B . w of the returned rows (NaN on status 3 / 4)."""
     K, Dm, A = _check_risk_model("risk_mvo_books", B, Fc, S2)
     if not _is_f64_device(X, (2,), B.device):
         raise _lib.FmxError("risk_mvo_books: X must be a float64 [J][A] tensor on B's device")
@@ -1274,9 +1278,23 @@ def risk_mvo_books(B, Fc, S2, X, present=None, model_row=None, max_weight=0.03, 
     if tuple(model_row.shape) != (J,):
         raise _lib.FmxError(f"risk_mvo_books: model_row must be [{J}]")
     W, counts, info = _mvo_outputs((J,), (A, 2, 6), X.device)
-    call("fmx_risk_mvo_books", ptr(B), ptr(Fc), ptr(S2), int(K), int(Dm), int(A), ptr(model_row), ptr(X), ptr(present),
-         int(J), float(max_weight), int(max_iter), float(eps), ptr(W), ptr(counts), ptr(info), stream_ptr())
-    return W, counts, info
+    mask = 0
+    for k in (() if neutral is None else neutral):
+        if not 0 <= int(k) < K:
+            raise _lib.FmxError(f"risk_mvo_books: neutral factor {k} outside [0, {K})")
+        mask |= 1 << int(k)
+    if mask == 0 and not return_expo:
+        call("fmx_risk_mvo_books", ptr(B), ptr(Fc), ptr(S2), int(K), int(Dm), int(A), ptr(model_row), ptr(X),
+             ptr(present), int(J), float(max_weight), int(max_iter), float(eps), ptr(W), ptr(counts), ptr(info),
+             stream_ptr())
+        return W, counts, info
+    expo = torch.empty((J, K), dtype=F64, device=X.device) if return_expo else None
+    nb = int(_lib.load().fmx_risk_mvo_neutral_books_work_bytes(A, K, J))
+    work, wb = _workspace_bytes(X.device, nb)
+    call("fmx_risk_mvo_neutral_books", ptr(B), ptr(Fc), ptr(S2), int(K), int(Dm), int(A), ptr(model_row), ptr(X),
+         ptr(present), int(J), mask, float(max_weight), int(max_iter), float(eps), ptr(W), ptr(counts), ptr(info),
+         ptr(expo), ptr(work), wb, stream_ptr())
+    return (W, counts, info, expo) if return_expo else (W, counts, info)
 
 
 def _mvo_turnover_inputs(fn, R0, win_rows, win_T, X, present, W, return_opt, chain_windows):

@@ -20,9 +20,12 @@
 ``FactorRiskModel.fit`` keeps the three device arrays (``B`` [K][D][A], ``Fc`` [D][K][K],
 ``S2`` [D][A]) and the ``panel_index``; ``portfolio_risk`` / ``risk_contributions`` /
 ``marginal_risk`` are one ``engine.risk_books`` pass, and ``simulation.risk_mvo_trade_list``
-optimises ``Simulation(method="mvo")`` against the model (``engine.risk_mvo_books``).
+optimises ``Simulation(method="mvo")`` against the model (``engine.risk_mvo_books``);
+``model.neutral_to(names)`` makes those books neutral to factors of the model.
 """
 from __future__ import annotations
+
+import copy
 
 import numpy as np
 import pandas as pd
@@ -71,6 +74,19 @@ class FactorRiskModel:
     @property
     def K(self):
         return len(self.columns)
+
+    neutral = ()        # the factors ``simulation.risk_mvo_trade_list`` holds its books neutral to
+
+    def neutral_to(self, names):
+        """A shallow view of the model (the same device arrays and frames, no copy) whose MVO
+        books are neutral to the factors ``names`` of ``columns``."""
+        names = (names,) if isinstance(names, str) else tuple(names)
+        unknown = [n for n in names if n not in self.columns]
+        if unknown:
+            raise ValueError(f"neutral_to: {unknown} are not factors of the model ({list(self.columns)})")
+        view = copy.copy(self)
+        view.neutral = names
+        return view
 
     @classmethod
     def fit(cls, factors_df: pd.DataFrame, returns: pd.Series, lag: int = 1, cov_halflife: float = 126,

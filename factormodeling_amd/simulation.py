@@ -33,6 +33,7 @@ methods run on the device, shared by ``Simulation`` and ``multi_manager``.
 """
 from __future__ import annotations
 
+import logging
 import os
 
 import numpy as np
@@ -232,13 +233,24 @@ def mvo_trade_list(custom_feature: pd.Series, returns: pd.Series, pct: float = 0
 
 
 def risk_mvo_trade_list(custom_feature: pd.Series, model, pct: float = 0.1, max_weight: float = 0.03,
-                        return_info: bool = False, max_iter: int = 20000, eps: float = 1e-9):
+                        return_info: bool = False, max_iter: int = 20000, eps: float = 1e-9, neutral=None):
     """``mvo_trade_list`` against a fitted ``risk_model.FactorRiskModel`` instead of the returns
     window: every date's book minimises w'Sigma w under the model's Sigma of that date
     (engine.risk_mvo_books), with the constraints, statuses and the
     ``(shifted, counts_df[, extra])`` result of ``mvo_trade_list``.  A date the model does not
     have, or has as invalid, carries the equal-weight book (status 4).  The feature's symbols
-    must be symbols of the model."""
+    must be symbols of the model.
+
+    ``neutral`` (default: ``model.neutral``, see ``FactorRiskModel.neutral_to``): names of model
+    factors every solved book is also neutral to, B_k . w = 0.  A date on which the
+    legs, the box and neutrality cannot hold together ends at ``max_iter`` with status 1 and its
+    last iterate; one warning per call names such dates.  ``extra`` then also holds ``expo``
+    [D][K], the exposures of the books to every factor, and ``neutral``, the names."""
+    neutral = tuple(model.neutral if neutral is None else ((neutral,) if isinstance(neutral, str) else neutral))
+    nidx = model.columns.get_indexer(list(neutral))
+    if (nidx < 0).any():
+        raise ValueError(f"risk_mvo_trade_list: {[n for n, k in zip(neutral, nidx) if k < 0]} are not factors "
+                         f"of the risk model ({list(model.columns)})")
     custom_feature = by_date(custom_feature)
     dev = device()
     pi = panel_index(custom_feature.index)
@@ -255,7 +267,13 @@ def risk_mvo_trade_list(custom_feature: pd.Series, model, pct: float = 0.1, max_
     ok = model.valid.to_numpy()
     mrow[mrow >= 0] = np.where(ok[mrow[mrow >= 0]], mrow[mrow >= 0], -1)
     X, present = torch.as_tensor(xh, device=dev), torch.as_tensor(ph, device=dev)
-    W, counts, info = E.risk_mvo_books(model.B, model.Fc, model.S2, X, present, mrow, max_weight, max_iter, eps)
+    expo = None
+    if len(neutral):
+        W, counts, info, expo = E.risk_mvo_books(model.B, model.Fc, model.S2, X, present, mrow, max_weight, max_iter,
+                                                 eps, neutral=nidx, return_expo=True)
+        _warn_not_neutral(model, pi.dates, mrow, X, present, info, expo, nidx)
+    else:
+        W, counts, info = E.risk_mvo_books(model.B, model.Fc, model.S2, X, present, mrow, max_weight, max_iter, eps)
     eq = info[:, 0] == 4
     if bool(eq.any()):
         _, ce, we = E.trade_books(X[None], "equal", pct, max_weight, present=present, nan_absent=False, raw=True)
@@ -270,9 +288,31 @@ def risk_mvo_trade_list(custom_feature: pd.Series, model, pct: float = 0.1, max_
     counts_df = pd.DataFrame({"long_count": cn[:, 0].astype(np.int64), "short_count": cn[:, 1].astype(np.int64)},
                              index=pd.Index(pi.dates, name=custom_feature.index.names[0]))
     if return_info:
-        return shifted, counts_df, {"info": info.cpu().numpy(), "books": W.cpu().numpy()[:, scol], "dates": pi.dates,
-                                    "symbols": pi.symbols}
+        extra = {"info": info.cpu().numpy(), "books": W.cpu().numpy()[:, scol], "dates": pi.dates, "symbols": pi.symbols}
+        if expo is not None:
+            extra.update(expo=expo.cpu().numpy(), neutral=neutral)
+        return shifted, counts_df, extra
     return shifted, counts_df
+
+
+def _warn_not_neutral(model, dates, mrow, X, present, info, expo, nidx):
+    """One warning naming the dates that ran to max_iter (status 1) with an exposure to a
+    neutral factor k above 1e-8 max|B_k| (the maximum over the date's active cells)."""
+    st1 = np.flatnonzero(info[:, 0].cpu().numpy() == 1)
+    if not len(st1):
+        return
+    rows = torch.as_tensor(mrow[st1], dtype=torch.long, device=expo.device)
+    k = torch.as_tensor(nidx, dtype=torch.long, device=expo.device)
+    Bn = torch.nan_to_num(model.B[k][:, rows], nan=0.0, posinf=0.0, neginf=0.0)        # [n][dates][A]
+    active = (present[st1] != 0) & ((X[st1] > 0) | (X[st1] < 0))
+    bmax = (Bn.abs() * active).amax(dim=2).T                                            # [dates][n]
+    off = (expo[st1][:, k].abs() > 1e-8 * bmax).any(dim=1).cpu().numpy()
+    if off.any():
+        names = ", ".join(str(pd.Timestamp(d).date()) if isinstance(d, np.datetime64) else str(d)
+                          for d in np.asarray(dates)[st1[off]])
+        logging.getLogger("simulation").warning(
+            "risk_mvo_trade_list: %d date(s) reached max_iter without a book neutral to %s (the constraints may be "
+            "infeasible there): %s", int(off.sum()), list(model.columns[nidx]), names)
 
 
 # ----------------------------------------------------------------------------- routing

@@ -679,6 +679,22 @@ fmx_status fmx_risk_mvo_books(const double* B, const double* Fc, const double* S
                               const int32_t* model_row, const double* X, const uint8_t* present, int64_t J,
                               double max_weight, int32_t max_iter, double eps, double* W, double* counts, double* info,
                               void* stream);
+/* fmx_risk_mvo_books with the book also neutral to factors of the model: on the
+ * active cells B_k . w = 0 for every factor k whose bit is set in neutral_mask (a bit at or
+ * above K is FMX_ERR_ARG; B read as above).  The rows enter the x-step exactly through K x K
+ * algebra.  A neutral row with no exposure on the active cells, or dependent on the legs and
+ * the rows before it, is dropped; a non-finite or indefinite system of the rows is status 2.
+ * Status 0 also needs |B_k . w| <= eps max|B_k| for every k of the mask.  Neutrality can make
+ * the constraints infeasible; no test is made: such a date ends with status 1 at max_iter.
+ *   expo [J][K] or NULL: B . w of the returned row over all K factors (NaN on status 3 / 4).
+ * neutral_mask == 0 is fmx_risk_mvo_books itself (the same kernel, the same bytes).  The
+ * set-up runs in LDS: the work_bytes function returns 0 and work is not read. */
+int64_t fmx_risk_mvo_neutral_books_work_bytes(int64_t A, int64_t K, int64_t J);
+fmx_status fmx_risk_mvo_neutral_books(const double* B, const double* Fc, const double* S2, int64_t K, int64_t Dm,
+                                      int64_t A, const int32_t* model_row, const double* X, const uint8_t* present,
+                                      int64_t J, uint32_t neutral_mask, double max_weight, int32_t max_iter, double eps,
+                                      double* W, double* counts, double* info, double* expo, void* work,
+                                      int64_t work_bytes, void* stream);
 
 /* ---- portfolio P&L (portfolio_simulation.py:748-819) ---------- */
 /* Replaces Simulation._daily_portfolio_returns' per-date sums on the aligned [D][A] grid

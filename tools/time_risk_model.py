@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Times of the factor risk model's two kernels on synthetic panels.
 
-    python tools/time_risk_model.py [--risk 2520x5000] [--mvo 500x1000,2520x5000] [--K 8,32] [--out FILE]
+    python tools/time_risk_model.py [--risk 2520x5000] [--mvo 500x1000,2520x5000] [--K 8,32] [--neutral 1,8,K]
+                                      [--out FILE]
 
 * ``risk_books`` (fmx_risk_books) at ``--risk`` with K = 32 and M = 1 / 32 books: ms between two
   device events (a warm-up, then the median of ``--reps`` runs) and the bytes it must read
@@ -10,7 +11,10 @@
 * ``risk_mvo_books`` (fmx_risk_mvo_books) at every ``--mvo`` size and K: ms, mean / max ADMM
   iterations and the iteration histogram; ``sim_mvo_books`` (fmx_sim_mvo_books, a 60-row
   returns window, shrinkage 0.1) on the same signal panel in the same process -- the only
-  meaningful comparison: the same QP under the other covariance.
+  meaningful comparison: the same QP under the other covariance;
+* with ``--neutral 1,8,K`` the same books neutral to the first n factors
+  (fmx_risk_mvo_neutral_books): ms, iterations, statuses and ms per mean iteration
+  beside the un-neutral call's at the same shape in the same process.
 Signals N(0, 1), exposures N(0, 1) with 0.1 % NaN, Fc = Q Q' 1e-4, s2 = (0.01 U(0.3, 2))^2,
 box 0.03.  One JSON line per case.
 """
@@ -64,6 +68,7 @@ def main():
     ap.add_argument("--risk", default="2520x5000")
     ap.add_argument("--mvo", default="500x1000,2520x5000")
     ap.add_argument("--K", default="8,32")
+    ap.add_argument("--neutral", default="", help="numbers of neutral factors (the first n; 'K' = all), e.g. 0,1,8,K")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -116,6 +121,15 @@ def main():
             B, Fc, S2 = make_model(torch, D, A, K, dev)
             ms, out = _events(torch, lambda: E.risk_mvo_books(B, Fc, S2, X, None, None, 0.03), args.reps)
             emit(dict(op="risk_mvo_books", D=D, A=A, K=K, ms=ms, sim_mvo_books_ms=ms0, **_iters(out[2])))
+            base = ms / (float(out[2][:, 1].sum()) / D)                    # ms per mean iteration, the comparator
+            for n in sorted({min(int(v) if v != "K" else K, K) for v in args.neutral.split(",") if v}):
+                if n == 0:
+                    continue                                               # the empty mask is the call above
+                msn, outn = _events(torch, lambda: E.risk_mvo_books(B, Fc, S2, X, None, None, 0.03, neutral=range(n),
+                                                                    return_expo=True), args.reps)
+                it = _iters(outn[2])
+                emit(dict(op="risk_mvo_books_neutral", D=D, A=A, K=K, neutral=n, ms=msn, un_neutral_ms=ms,
+                          ms_per_mean_iter=msn / it["iters_mean"], un_neutral_ms_per_mean_iter=base, **it))
             del B, Fc, S2
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
