@@ -29,6 +29,7 @@ SIGNATURES = {
     "fmx_ts_order": [c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_dbl, c_i32, c_vp, c_vp],
     "fmx_ts_ewm": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_dbl, c_i32, c_i32,
                    c_i32, c_vp, c_vp],
+    "fmx_ts_moment": [c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp],
     "fmx_ts_set": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp],
     "fmx_ts_corr": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp],
     "fmx_ts_corr_vol_feature": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp],
@@ -151,6 +152,7 @@ _RESTYPES = {"fmx_last_error": c_cp, "fmx_build_variant": c_cp, "fmx_ic_ranked_w
 TS = dict(sum=0, mean=1, std=2, var=3, zscore=4, rank=5, decay=6, diff=7, delay=8, backfill=9)
 TSO = dict(min=0, max=1, argmin=2, argmax=3, median=4, quantile=5)
 TSO_INTERP = dict(linear=0, lower=1, higher=2, midpoint=3, nearest=4)
+TSM = dict(skew=0, kurt=1, cov=2)
 EWM = dict(mean=0, var=1, std=2, zscore=3, cov=4, corr=5)     # fmx_ts_ewm's outputs, in argument order
 CS = dict(zscore=0, mean=1, market_neutralize=2, stats=3)
 RANK = dict(average=0, min=1, max=2, first=3, dense=4, scipy_average=5)

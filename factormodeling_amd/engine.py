@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CS, CSREG, EW, EWM, GROUP, RANK, TS, TSO, TSO_INTERP, call, ptr, stream_ptr
+from ._lib import CS, CSREG, EW, EWM, GROUP, RANK, TS, TSM, TSO, TSO_INTERP, call, ptr, stream_ptr
 
 F64 = torch.float64
 
@@ -75,6 +75,35 @@ def ts_order(op: str, X, window: int, present=None, q=0.5, interpolation="linear
     Y = _out(X, out)
     call("fmx_ts_order", TSO[op], ptr(X), ptr(Y), F, D, A, A, int(window), float(q), TSO_INTERP[interpolation],
          ptr(present), stream_ptr())
+    return Y
+
+
+def ts_moment(op: str, X, window: int, present=None, y=None, out=None):
+    """Rolling higher moment (fmx_ts_moment): ``op`` in skew / kurt / cov, pandas'
+    ``rolling(window).skew() / .kurt() / .cov(y)`` per symbol.  ``y`` is read for cov only: a
+    [D][A] series shared by all columns or a [F][D][A] panel, float64, on X's device."""
+    if op not in TSM:
+        raise ValueError(f"ts_moment: unknown op {op!r}")
+    if int(window) < 1:
+        raise ValueError("window must be >= 1")
+    if op == "cov" and y is None:
+        raise ValueError("ts_moment: cov needs y")
+    X = as3(X)
+    _check_panel(X)
+    F, D, A = X.shape
+    _check_present(present, D, A)
+    ystride = 0
+    if op != "cov":
+        y = None
+    else:
+        if not isinstance(y, torch.Tensor) or y.device != X.device or y.dtype != F64 or \
+                tuple(y.shape) not in ((D, A), (F, D, A)):
+            raise _lib.FmxError("y must be a float64 [D][A] or [F][D][A] tensor on X's device")
+        ystride = D * A if y.dim() == 3 else 0
+        y = y.contiguous()
+    Y = _out(X, out)
+    call("fmx_ts_moment", TSM[op], ptr(X), ptr(y), ptr(Y), F, D, A, A, ystride, int(window), ptr(present),
+         stream_ptr())
     return Y
 
 

@@ -28,7 +28,7 @@ from .profiling import phase
 
 __all__ = [
     "ts_sum", "ts_mean", "ts_std", "ts_zscore", "ts_rank", "ts_diff", "ts_delay", "ts_decay", "ts_backfill",
-    "ts_corr", "ts_min", "ts_max", "ts_argmin", "ts_argmax", "ts_median", "ts_quantile",
+    "ts_corr", "ts_skew", "ts_kurt", "ts_cov", "ts_min", "ts_max", "ts_argmin", "ts_argmax", "ts_median", "ts_quantile",
     "ts_ewm_mean", "ts_ewm_var", "ts_ewm_std", "ts_ewm_zscore", "ts_ewm_cov", "ts_ewm_corr", "cs_rank", "cs_winsor", "cs_filter_center", "cs_zscore", "cs_bool", "cs_mean", "sign", "power",
     "log", "abs_", "clip", "bucket", "group_mean", "group_neutralize", "group_normalize",
     "group_rank_normalized", "market_neutralize", "ts_regression_fast", "cs_regression",
@@ -128,6 +128,35 @@ def ts_corr(x, y, window: int):
     Yd = P.to_device(yv, dev)[0]
 
     return _panel_apply(x, lambda X, p: engine.ts_corr(X, Yd, window, p))
+
+
+# ---- rolling higher moments (builder-defined, no reference counterpart; pinned to pandas) ----
+def ts_skew(series, window: int):
+    """Per-symbol ``x.rolling(window).skew()``; all NaN for ``window < 3``.  pandas centres a
+    symbol's series by the rounded mean of all its rows, so the last bits of a value can depend
+    on later rows."""
+    return _panel_apply(series, lambda X, p: engine.ts_moment("skew", X, window, p))
+
+
+def ts_kurt(series, window: int):
+    """Per-symbol ``x.rolling(window).kurt()`` (excess kurtosis); all NaN for ``window < 4``.
+    Centred as ts_skew."""
+    return _panel_apply(series, lambda X, p: engine.ts_moment("kurt", X, window, p))
+
+
+def ts_cov(x, y, window: int):
+    """Per-symbol ``x.rolling(window).cov(y)`` (ddof 1); ``y`` is aligned to ``x``'s index.  A
+    Series ``y`` is shared by all columns of a DataFrame ``x``; a DataFrame ``y`` with ``x``'s
+    columns pairs column with column."""
+    per_column = isinstance(y, pd.DataFrame)
+    if per_column:
+        if not isinstance(x, pd.DataFrame) or list(y.columns) != list(x.columns):
+            raise ValueError("ts_cov: a DataFrame y needs a DataFrame x with the same columns")
+    yv = y.reindex(x.index).to_numpy(dtype=np.float64, na_value=np.nan)
+    Yd = panel_index(x.index).to_device(yv, device())
+    if not per_column:
+        Yd = Yd[0]
+    return _panel_apply(x, lambda X, p: engine.ts_moment("cov", X, window, p, Yd))
 
 
 # ---- rolling order statistics (builder-defined, no reference counterpart; pinned to pandas) ----

@@ -75,6 +75,11 @@ typedef int32_t fmx_status;
 #define FMX_TSO_MIDPOINT 3
 #define FMX_TSO_NEAREST 4
 
+/* rolling higher moments (fmx_ts_moment; builder-defined, pandas semantics) */
+#define FMX_TSM_SKEW 0     /* ts_skew     rolling(w).skew()                              */
+#define FMX_TSM_KURT 1     /* ts_kurt     rolling(w).kurt()   (excess kurtosis)          */
+#define FMX_TSM_COV 2      /* ts_cov      rolling(w).cov(y)   (ddof 1)                   */
+
 /* cross-sectional moment ops (fmx_cs_moment) */
 #define FMX_CS_ZSCORE 0            /* operations.py:77  cs_zscore         */
 #define FMX_CS_MEAN 1              /* operations.py:85  cs_mean           */
@@ -170,6 +175,24 @@ fmx_status fmx_ts_ewm(const double* X, const double* Ycol, double* Omean, double
                       double* Ozscore, double* Ocov, double* Ocorr, int64_t F, int64_t D, int64_t A, int64_t ld,
                       double com, int32_t adjust, int32_t ignore_na, int32_t min_periods, const uint8_t* present,
                       void* stream);
+
+/* Builder-defined rolling higher moments (no reference counterpart): per symbol, over its own
+ * present rows in date order, x.rolling(window).skew() / .kurt() / .cov(y) of pandas 2.3
+ * (min_periods = window, cov with ddof 1), bit-identical as values, NaN pattern included.
+ * +-inf count as NaN.  An absent cell (present == 0) is no row of its symbol and its output
+ * is NaN.  Any window >= 1: FMX_TSM_SKEW is all NaN for window < 3, FMX_TSM_KURT for
+ * window < 4, FMX_TSM_COV for window < 2.  Ycol is read for FMX_TSM_COV only: one [D][ld]
+ * series shared by all F columns (y_fstride 0) or [F][D][ld] (y_fstride = D * ld).
+ * skew / kurt centre a symbol's series as pandas does, by C round() of the mean of ALL its
+ * rows (unless its minimum lies 1e5 / 1e4 below the mean): where |mean| >= 0.5 the last bits
+ * of a value can depend on later rows, so a date-subset of a panel need not reproduce them.
+ * Overflow of x^3 / x^4, and of a product x y of two finite values, is not pinned.  One
+ * streaming pass per (column, symbol) (skew / kurt: two reads of X), dense or ragged; no
+ * scratch.  Y may not alias X or Ycol.  A null panel, ld < A, window < 1, FMX_TSM_COV
+ * without Ycol and an unknown op are refused before any device work. */
+fmx_status fmx_ts_moment(int32_t op, const double* X, const double* Ycol, double* Y, int64_t F, int64_t D,
+                         int64_t A, int64_t ld, int64_t y_fstride, int32_t window, const uint8_t* present,
+                         void* stream);
 
 /* Builder-defined ts_corr (no reference counterpart): per-symbol rolling Pearson of X[f]
  * against Ycol (y_fstride = 0: one [D][ld] series shared by all factors, e.g. returns),
