@@ -135,6 +135,8 @@ SIGNATURES = {
     "fmx_risk_mvo_neutral_books": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_u32, c_dbl, c_i32,
                                    c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "fmx_risk_mvo_neutral_books_work_bytes": [c_i64, c_i64, c_i64],
+    "fmx_perf_stats": [c_vp, c_i64, c_i64, c_i64, c_dbl, c_vp, c_vp, c_vp, c_vp],
+    "fmx_perf_periods": [c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp],
 }
 _RESTYPES = {"fmx_last_error": c_cp, "fmx_build_variant": c_cp, "fmx_ic_ranked_work_len": c_i64, "fmx_rank_ic_work_len": c_i64, "fmx_gram_work_bytes": c_i64, "fmx_gram_direct_work_bytes": c_i64,
              "fmx_gram_direct_exact_work_bytes": c_i64, "fmx_ic_daily_sorted_work_bytes": c_i64,
@@ -159,6 +161,11 @@ RANK = dict(average=0, min=1, max=2, first=3, dense=4, scipy_average=5)
 GROUP = dict(mean=0, neutralize=1, normalize=2, rank=3)
 EW = dict(sign=0, power=1, log=2, abs=3, clip=4, where=5)
 CSREG = dict(resid=0, beta=1, alpha=2, fitted=3, r2=4)
+# rows of fmx_perf_stats' [NSTAT][K] table (FMX_PERF_*), and its cap on the rows of a series
+PERF = dict(mean=0, std=1, max=2, min=3, count=4, ex_mean=5, ex_std=6, down_count=7, down_mean=8, down_std=9,
+            final=10, maxdd=11, maxdd_row=12, maxdd_peak_row=13, dd_run=14)
+PERF_NSTAT = 15
+PERF_TMAX = 16384
 
 
 class FmxError(RuntimeError):

@@ -1589,3 +1589,88 @@ def qbucket_mean(labels, R, n_groups: int, prev_row=None, rpresent=None):
     call("fmx_qbucket_mean", ptr(labels), ptr(R), ptr(rpresent), ptr(prev_row), ptr(mean), ptr(count), F, D, A, n,
          stream_ptr())
     return mean, count
+
+
+# ----------------------------------------------------------------------------- performance statistics
+PERF = _lib.PERF
+PERF_NSTAT = _lib.PERF_NSTAT
+PERF_TMAX = _lib.PERF_TMAX
+
+
+def _check_table(R, name="R"):
+    """A [K][T] float64 device table, one series per row with unit stride; rows may be padded
+    (a column slice of a wider contiguous table).  Returns the row stride ld >= T."""
+    if not isinstance(R, torch.Tensor) or R.device.type != "cuda":
+        raise _lib.FmxError(f"{name} must be a HIP device tensor")
+    if R.dtype != F64 or R.dim() != 2:
+        raise _lib.FmxError(f"{name} must be a float64 [K][T] tensor (one series per row)")
+    K, T = R.shape
+    if K < 1 or T < 1:
+        raise ValueError(f"{name} must hold at least one series and one row")
+    ld = R.stride(0) if K > 1 else T
+    if (T > 1 and R.stride(1) != 1) or ld < T:
+        raise _lib.FmxError(f"{name} must hold each series contiguously, rows at most padded")
+    return ld
+
+
+def _table_out(out, key, shape, R, ld=None):
+    """Output ``key``: the caller's tensor (checked) or a new one.  With ``ld`` the output is a
+    [K][T] curve that shares R's row stride."""
+    t = None if out is None else out.get(key)
+    if t is None:
+        if ld is None or ld == shape[1]:
+            return torch.empty(shape, dtype=F64, device=R.device)
+        return torch.empty((shape[0], ld), dtype=F64, device=R.device)[:, :shape[1]]
+    ok = (isinstance(t, torch.Tensor) and t.device == R.device and t.dtype == F64 and tuple(t.shape) == tuple(shape)
+          and t.data_ptr() != R.data_ptr())
+    if ok and ld is None:
+        ok = t.is_contiguous()
+    elif ok:
+        ok = _check_table(t, f"out[{key!r}]") == ld
+    if not ok:
+        raise _lib.FmxError(f"out[{key!r}] must be a distinct float64 {tuple(shape)} tensor on R's device"
+                            + ("" if ld is None else " with R's row stride"))
+    return t
+
+
+def perf_stats(R, rf_daily=0.0, curves=True, out=None):
+    """Performance statistics of K return series (fmx_perf_stats): R is [K][T] float64 SIMPLE
+    returns, one series per row (rows may be padded: the row stride is passed as ld), NaN = no
+    observation.  Returns ``(stats, cum, dd)``: stats [PERF_NSTAT][K] with the rows named by
+    ``PERF``, and with ``curves`` the cumulative-return and drawdown curves [K][T] with R's row
+    stride (None otherwise).  ``out`` may hold preallocated tensors under 'stats' / 'cum' / 'dd'.
+    pandas' bits per series, whatever K.  T <= PERF_TMAX."""
+    ld = _check_table(R)
+    K, T = R.shape
+    if T > PERF_TMAX:
+        raise ValueError(f"perf_stats: a series may hold at most {PERF_TMAX} rows (got {T})")
+    bad = set(out or ()) - {"stats", "cum", "dd"}
+    if bad:
+        raise ValueError(f"perf_stats: unknown outputs {sorted(bad)}")
+    stats = _table_out(out, "stats", (PERF_NSTAT, K), R)
+    cum = _table_out(out, "cum", (K, T), R, ld) if curves else None
+    dd = _table_out(out, "dd", (K, T), R, ld) if curves else None
+    if curves and cum.data_ptr() == dd.data_ptr():
+        raise _lib.FmxError("out['cum'] and out['dd'] must be distinct")
+    call("fmx_perf_stats", ptr(R), K, T, ld, float(rf_daily), ptr(stats), ptr(cum), ptr(dd), stream_ptr())
+    return stats, cum, dd
+
+
+def perf_periods(R, seg, nseg: int, out=None):
+    """Period returns of K return series (fmx_perf_periods): ``seg`` gives each of the T rows its
+    bucket, non-decreasing in [0, nseg) (checked here, on the host); returns [nseg][K], the
+    left-to-right product of 1 + R over a bucket's non-NaN rows minus 1 (0.0 for an empty one)."""
+    ld = _check_table(R)
+    K, T = R.shape
+    nseg = int(nseg)
+    if nseg < 1:
+        raise ValueError("perf_periods: nseg must be >= 1")
+    seg_h = seg.detach().cpu().numpy() if isinstance(seg, torch.Tensor) else np.asarray(seg)
+    if seg_h.shape != (T,) or seg_h.dtype.kind not in "iu":
+        raise ValueError("perf_periods: seg must be T integers")
+    if seg_h.min() < 0 or seg_h.max() >= nseg or (np.diff(seg_h.astype(np.int64)) < 0).any():
+        raise ValueError("perf_periods: seg must be non-decreasing with values in [0, nseg)")
+    seg_d = torch.as_tensor(np.ascontiguousarray(seg_h, dtype=np.int32), device=R.device)
+    O = _table_out(None if out is None else {"out": out}, "out", (nseg, K), R)
+    call("fmx_perf_periods", ptr(R), K, T, ld, ptr(seg_d), nseg, ptr(O), stream_ptr())
+    return O

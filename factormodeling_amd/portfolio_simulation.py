@@ -28,8 +28,11 @@ without a GPU or outside the kernels' caps: ``_daily_trade_list`` hands these to
 reference's ``Simulation``, loaded by file path from ``FMX_REFERENCE_DIR`` (the user's
 reference checkout; a module of the same name cannot sit on ``sys.path`` next to this
 drop-in), while the P&L and metrics of the resulting weights still run on the device.
-``PortfolioAnalyzer`` (reporting and plots) is the reference's own host module, imported
-from ``portfolio_analyzer`` when ``run()`` needs it.
+``PortfolioAnalyzer`` (reporting and plots) is imported from ``portfolio_analyzer`` when
+``run()`` needs it: with the drop-in directory on ``sys.path`` that is this package's class
+(``factormodeling_amd.portfolio_analyzer``, the statistics on the GPU, the reference's bits), and
+where no module of that name exists ``run()`` takes this package's class directly (an import
+error inside an existing ``portfolio_analyzer`` is raised, not hidden).
 """
 from __future__ import annotations
 
@@ -150,7 +153,12 @@ class Simulation:
 
     def run(self):
         """portfolio_simulation.py:73-95."""
-        from portfolio_analyzer import PortfolioAnalyzer   # the reference's host reporting module
+        try:
+            from portfolio_analyzer import PortfolioAnalyzer   # the drop-in (or the user's reference checkout)
+        except ModuleNotFoundError as e:
+            if e.name != "portfolio_analyzer":                 # a module of that name exists and failed to load
+                raise
+            from .portfolio_analyzer import PortfolioAnalyzer  # same class, same bits
         self.factors_df[self.name] = self.custom_feature
         self.custom_feature = self.custom_feature * self.investability_flag
         weights, counts = self._daily_trade_list()

@@ -823,6 +823,72 @@ fmx_status fmx_ts_ols(const double* Y, const double* X, const uint8_t* present, 
                       double* alpha, double* fitted, double* resid, double* r2, double* sigma, uint8_t* work,
                       void* stream);
 
+/* ---- performance statistics (portfolio_analyzer.py:9-81) ---------------- */
+/* Replaces the numbers of PortfolioAnalyzer (average_return ... min_daily_return, the
+ * cumulative and drawdown curves, monthly_return / yearly_return) for K series at once.
+ * Layout: R is [K][ld], ONE SERIES CONTIGUOUS (series k occupies R[k * ld .. k * ld + T)), the
+ * transpose of a dates x K table: a workgroup owns a series and reads it with unit stride.
+ * R holds SIMPLE returns (exp(log_return) - 1, taken on the host); NaN = no observation;
+ * +-inf is not pinned.  cum and dd are [K][ld] like R, either may be NULL (not written).
+ * Everything is pandas' own operation sequence on the series alone (pandas 2.3 without
+ * bottleneck), bit-identical as values, and does not depend on K or on the other series:
+ *   cum[t]  = cumprod of 1 + R over the non-NaN rows up to t, minus 1; NaN on a NaN row
+ *   dd[t]   = (cum[t] + 1) / peak[t] - 1, peak = cummax of cum + 1 over the non-NaN rows
+ * stats is [FMX_PERF_NSTAT][K] (stat s of series k at stats[s * K + k]):
+ *   MEAN, STD      Series.mean() / .std() (ddof 1) of R: numpy pairwise sums over the T
+ *                  NaN -> 0 masked values / count, then of (avg - v) * (avg - v) / (count - 1)
+ *   MAX, MIN       over the non-NaN rows;  COUNT  the number of non-NaN rows
+ *   EX_MEAN, EX_STD          the same mean / std of E = R - rf_daily
+ *   DOWN_COUNT, _MEAN, _STD  count, mean, std of the compacted E[E < 0] (date order), summed
+ *                  on numpy's pairwise schedule of ITS OWN length (Sortino's downside std)
+ *   FINAL          cum[T - 1] + 1 (NaN when the last row is NaN, as .iloc[-1] gives)
+ *   MAXDD          nanmin(dd)
+ *   MAXDD_ROW      builder-defined: the row of that minimum, first occurrence (-1: no row)
+ *   MAXDD_PEAK_ROW builder-defined: the earliest row at which the peak in force at MAXDD_ROW
+ *                  was attained (-1: no row)
+ *   DD_RUN         builder-defined: the longest run of non-NaN rows with dd < 0; NaN rows
+ *                  neither count nor break a run
+ * A count of 0 gives a NaN mean, max, min and MAXDD; a count of 0 or 1 a NaN std; a zero std
+ * is returned as 0 (the caller's ratio is then IEEE's +-inf or NaN).  Counts and rows are exact
+ * integers stored as doubles.  The ratios (Sharpe, Sortino), sqrt(trading days) and the
+ * annualising power final ** (1 / years) are the caller's host arithmetic.
+ * T <= FMX_PERF_TMAX (the downside series and the curve are staged in T doubles of LDS).  No
+ * scratch, no allocation (but the one-time pairwise schedule cache).  Null R or stats, K < 1,
+ * T < 1, ld < T, T > FMX_PERF_TMAX and cum / dd aliasing R or each other are refused before
+ * any device work. */
+#define FMX_PERF_TMAX 16384
+#define FMX_PERF_MEAN 0
+#define FMX_PERF_STD 1
+#define FMX_PERF_MAX 2
+#define FMX_PERF_MIN 3
+#define FMX_PERF_COUNT 4
+#define FMX_PERF_EX_MEAN 5
+#define FMX_PERF_EX_STD 6
+#define FMX_PERF_DOWN_COUNT 7
+#define FMX_PERF_DOWN_MEAN 8
+#define FMX_PERF_DOWN_STD 9
+#define FMX_PERF_FINAL 10
+#define FMX_PERF_MAXDD 11
+#define FMX_PERF_MAXDD_ROW 12
+#define FMX_PERF_MAXDD_PEAK_ROW 13
+#define FMX_PERF_DD_RUN 14
+#define FMX_PERF_NSTAT 15
+fmx_status fmx_perf_stats(const double* R, int64_t K, int64_t T, int64_t ld, double rf_daily, double* stats,
+                          double* cum, double* dd, void* stream);
+
+/* Period returns (portfolio_analyzer.py:62-68, resample(...).apply(lambda x: (1 + x).prod() - 1))
+ * of the same [K][ld] table.  seg is a DEVICE int32[T]: the bucket of each row, non-decreasing,
+ * in [0, nseg) (calendar months or years counted from the first date's, built by the caller).
+ * out is [nseg][K]: out[s * K + k] = the left-to-right product of 1 + R over the bucket's
+ * non-NaN rows, minus 1; a bucket with no row, or only NaN rows, gives exactly 0.0.
+ * seg is TRUSTED: the entry point cannot read device memory without a synchronisation, so the
+ * caller checks it (the Python layer does, on the host copy it uploads).  A seg that breaks the
+ * contract gives unspecified values but no access outside the T rows.  No cap on T, no
+ * scratch.  Null pointers, K < 1, T < 1, ld < T and nseg < 1 are refused before any device
+ * work. */
+fmx_status fmx_perf_periods(const double* R, int64_t K, int64_t T, int64_t ld, const int32_t* seg, int32_t nseg,
+                            double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
